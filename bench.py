@@ -22,12 +22,22 @@ pass A (hash + bin) and pass B (LDS tile OR + bitmap write).  Workloads:
 
 Multi-GPU: one process per GPU (torch.distributed.run).  No workload has a
 collective on its data path -- each rank owns whole filters.  RCCL reduces the
-key counter (sum) and the elapsed time (max).  The default workload also
-reports configs[3] as a `compaction_strong` sub-record (256 tables split over
-the N GPUs, strong scaling), the north star's multi-GPU target, the same
-build in a process serving Gets (`headline_with_reader`), and configs[4] and
-configs[2] as `probe` and `varlen` sub-records, each with its own parity,
-roofline and CPU baseline.  Rank 0 prints one JSON line.
+key counter (sum) and the elapsed time (max).  Rank 0 prints one JSON line.
+
+A plain run does what the headline figure needs and no more: set-up, the
+warm-up, the K timed steps, the output dump if --dump-outputs DIR is given
+(what the last timed step returned, as DIR/<name>.npy), and the result line
+(metric, value, unit, ms_per_step, ...).
+
+--full adds everything else to that line: the same K steps again with
+per-kernel HIP events (the roofline), parity against the reference / oracle
+pins, the measured HBM rates, the end-to-end figures and the CPU baseline;
+and, for the default workload, configs[3] as a `compaction_strong` sub-record
+(256 tables split over the N GPUs, strong scaling), the north star's
+multi-GPU target, the same build in a process serving Gets
+(`headline_with_reader`), and configs[4] and configs[2] as `probe` and
+`varlen` sub-records, each with its own parity, roofline and CPU baseline.
+The --no-* options switch parts of --full off.
 """
 import argparse
 import hashlib
@@ -49,7 +59,7 @@ COMPACTION_TABLES = 256   # BASELINE.json configs[3]
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -57,16 +67,21 @@ def parse():
     ap.add_argument("--workload", default="single", choices=["single", "compaction", "varlen", "probe"])
     ap.add_argument("--keys", type=int, default=10_000_000, help="keys per filter (single/varlen)")
     ap.add_argument("--queries", type=int, default=100_000_000, help="total probe queries (probe)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-kernel roofline, parity, e2e, CPU baselines and, for the "
+                         "default workload, the compaction_strong, headline_with_reader, probe and varlen records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the end-to-end records")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (--full)")
     ap.add_argument("--no-compaction-strong", action="store_true",
-                    help="single: skip the configs[3] compaction_strong sub-record")
+                    help="single, --full: skip the configs[3] compaction_strong sub-record")
     ap.add_argument("--no-sub-records", action="store_true",
-                    help="single: skip the configs[4] probe and configs[2] varlen sub-records")
+                    help="single, --full: skip the configs[4] probe and configs[2] varlen sub-records")
     ap.add_argument("--no-reader", action="store_true",
-                    help="single: skip the headline_with_reader record")
-    return ap.parse_args()
+                    help="single, --full: skip the headline_with_reader record")
+    return ap.parse_args(argv)
 
 
 def log(rank, *a):
@@ -227,6 +242,18 @@ class Workload:
             return self.builder.build(self.keys, self.offs)
         return self.builder.build(self.keys)
 
+    def outputs(self, out):
+        """What a caller of step() receives, by name: 1-D device tensors
+        (--dump-outputs).  A segmented build's bitmaps are joined at their exact
+        lengths, so the allocation's padding between them stays out."""
+        import torch
+
+        if self.kind == "probe":
+            return {"answers": out}
+        if self.kind == "compaction":
+            return {"bitmaps": torch.cat([self.builder.bitmap(i) for i in range(len(self.tables))])}
+        return {"bitmap": out}
+
     def step_routed(self):
         """The routed probe (N > 1): this rank's slice of the batch goes to the
         tables' owners and the answers come back, two RCCL all-to-alls."""
@@ -242,6 +269,44 @@ class Workload:
                             model_offrank_fraction=round((self.world - 1) / self.world, 4))
         return out
 
+
+
+DUMP_SAMPLE = 8_000_000  # elements of a sampled output: 32 MB as float32
+DUMP_FOLDS = 4_000_000   # at most this many sums in <name>_fold.npy: 16 MB
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(d, outputs, rank=0, world=1, sample=DUMP_SAMPLE, folds=DUMP_FOLDS):
+    """--dump-outputs: every named 1-D tensor as d/<name>.npy in float32 (at
+    N > 1, <name>_rank<r>.npy), so that two builds run with the same arguments
+    can be compared output for output.  An output of up to `sample` elements is
+    written whole.  A larger one is written as its elements at `sample` fixed
+    positions (drawn once from DUMP_SEED, sorted: the same in every run),
+    beside <name>_fold.npy: the sums of consecutive runs of W elements, W the
+    least power of two >= 64 that leaves at most `folds` sums, which cover all
+    of it (uint8 elements: exact in float32 for W <= 65536).  The two stay
+    under 64 MB."""
+    import torch
+
+    os.makedirs(d, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, t in outputs.items():
+        t = t.reshape(-1)
+        n = t.numel()
+        if n <= sample:
+            np.save(os.path.join(d, f"{name}{sfx}.npy"), t.cpu().numpy().astype(np.float32))
+            continue
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, sample))
+        picked = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(d, f"{name}{sfx}.npy"), picked.cpu().numpy().astype(np.float32))
+        width = 64
+        while (n + width - 1) // width > folds:
+            width *= 2
+        whole = n // width * width
+        sums = [t[:whole].view(-1, width).sum(dim=1, dtype=torch.int64)]
+        if whole < n:
+            sums.append(t[whole:].sum(dtype=torch.int64).reshape(1))
+        np.save(os.path.join(d, f"{name}_fold{sfx}.npy"), torch.cat(sums).cpu().numpy().astype(np.float32))
 
 
 def _cpu_cores():
@@ -729,13 +794,46 @@ def stream_gbs_once():
     return _STREAM_GBS[0]
 
 
+def headline_record(kind, args, w, world, backend, total_keys, elapsed_max):
+    """The result line of a plain run: the throughput of the K timed steps."""
+    probe = kind == "probe"
+    if probe:
+        metric = "Mqueries/s bloom-filter probe (device-resident), 16B keys, 256 filters, bits/key=10"
+        if world > 1:
+            metric += ", owner-bucketed"
+    elif kind == "varlen":
+        metric = "Mkeys/s bloom-filter build (device-resident), var-len keys, bits/key=10"
+    elif kind == "compaction":
+        metric = ("Mkeys/s bloom-filter build (device-resident), 16B keys, bits/key=10, "
+                  "configs[3]: 256 SSTables x 1M keys")
+    else:
+        metric = "Mkeys/s bloom-filter build (device-resident), 16B keys, bits/key=10"
+    return {
+        "metric": metric,
+        "value": round(total_keys / elapsed_max / 1e6, 1),
+        "unit": "Mqueries/s" if probe else "Mkeys/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed_max / max(args.steps, 1) * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if kind in ("probe", "compaction") else "weak",
+        "vs_baseline": None,
+        "dtype": w.dtype,
+        "data": "synthetic (SplitMix64 keys generated on device, SURVEY.md §8d)",
+        "config": dict(w.config, parallelism=f"whole filters per GPU x{world}, no data-path collective"),
+        "world": {"size": world, "backend": backend or "none (one process)"},
+    }
+
+
 def measure(kind, args, rank, world, backend, barrier, timed, sub=False):
-    """One workload's record: warmup, the timed K steps (the throughput), the
+    """One workload's record: warmup, the timed K steps (the throughput) and,
+    when asked, the dump of the last step's output; with --full also the
     same K steps again with per-kernel HIP events (the roofline), parity
     against the reference / oracle pins, and (rank 0, one GPU) its CPU
     baseline.  All ranks call; rank 0 gets the dict, the others None.
     sub: a sub-record of the default line (smaller CPU-baseline budget, no
-    e2e)."""
+    e2e, no dump)."""
     import torch
 
     import adlbloom as ab
@@ -757,6 +855,17 @@ def measure(kind, args, rank, world, backend, barrier, timed, sub=False):
         out = w.step()
     barrier()
     elapsed = time.perf_counter() - t0
+
+    # RCCL: the only collective -- sum of keys built, max of elapsed time
+    total_keys, elapsed_max = D.reduce_throughput(float(w.n) * args.steps, elapsed, device="cuda")
+    if args.dump_outputs and not sub:
+        dump_outputs(args.dump_outputs, w.outputs(out), rank, world)
+    if not args.full:  # a plain run: the headline record and nothing else
+        rec = headline_record(kind, args, w, world, backend, total_keys, elapsed_max) if rank == 0 else None
+        del w
+        torch.cuda.empty_cache()
+        return rec
+
     # Pass 2, the kernel durations: the same K steps again, each kernel timed by
     # HIP events on its own dispatch packets (build) or on torch's current
     # stream around the probe pipeline (Workload._probe_local).
@@ -773,9 +882,6 @@ def measure(kind, args, rank, world, backend, barrier, timed, sub=False):
     probe_ms = sum(a.elapsed_time(b) for a, b in w.kernel_events) / max(args.steps, 1) if probe else 0.0
     if probe:  # the kernel's own work: the queries this rank probed (its filters' share of all ranks')
         w.bytes_per_launch = ALGO_BYTES_PER_QUERY * w.served
-
-    # RCCL: the only collective -- sum of keys built, max of elapsed time
-    total_keys, elapsed_max = D.reduce_throughput(float(w.n) * args.steps, elapsed, device="cuda")
 
     # the routed probe (N > 1), reported beside the owner-bucketed measurement
     routing_variant = None
@@ -825,33 +931,9 @@ def measure(kind, args, rank, world, backend, barrier, timed, sub=False):
         achieved = w.bytes_per_launch / (kern_ms * 1e-3) / 1e9 if is_timed else None
         traffic = load_traffic(kind, w.bytes_per_launch)
         stream_gbs = stream_gbs_once()
-        if probe:
-            metric = "Mqueries/s bloom-filter probe (device-resident), 16B keys, 256 filters, bits/key=10"
-            if world > 1:
-                metric += ", owner-bucketed"
-        elif kind == "varlen":
-            metric = "Mkeys/s bloom-filter build (device-resident), var-len keys, bits/key=10"
-        elif kind == "compaction":
-            metric = ("Mkeys/s bloom-filter build (device-resident), 16B keys, bits/key=10, "
-                      "configs[3]: 256 SSTables x 1M keys")
-        else:
-            metric = "Mkeys/s bloom-filter build (device-resident), 16B keys, bits/key=10"
-        rec = {
-            "metric": metric,
-            "value": round(total_keys / elapsed_max / 1e6, 1),
-            "unit": "Mqueries/s" if probe else "Mkeys/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed_max / max(args.steps, 1) * 1e3, 4),
+        rec = headline_record(kind, args, w, world, backend, total_keys, elapsed_max)
+        rec.update({
             "ms_per_step_kernel_timed": round(elapsed_instrumented / max(args.steps, 1) * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if kind in ("probe", "compaction") else "weak",
-            "vs_baseline": None,
-            "dtype": w.dtype,
-            "data": "synthetic (SplitMix64 keys generated on device, SURVEY.md §8d)",
-            "config": dict(w.config, parallelism=f"whole filters per GPU x{world}, no data-path collective"),
-            "world": {"size": world, "backend": backend or "none (one process)"},
             "roofline": {
                 "bound": "hbm",
                 "achieved": round(achieved, 1) if achieved else None,
@@ -873,7 +955,7 @@ def measure(kind, args, rank, world, backend, barrier, timed, sub=False):
                 "frac_of_measured_stream_read": round(achieved / stream_gbs, 4) if (achieved and stream_gbs) else None,
             },
             "parity": parity,
-        }
+        })
         if traffic and is_timed:
             rec["roofline"]["traffic_gbs"] = round(traffic / (kern_ms * 1e-3) / 1e9, 1)
             rec["roofline"]["traffic_over_algorithmic"] = round(traffic / w.bytes_per_launch, 3)
@@ -983,8 +1065,8 @@ def with_reader(args, rank, world, timed):
     return rec
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     import torch
     import torch.distributed as dist
 
@@ -1030,7 +1112,7 @@ def main():
 
     out_json = measure(args.workload, args, rank, world, backend, barrier, timed)
 
-    if args.workload == "single":
+    if args.workload == "single" and args.full:
         # configs[3] beside the headline: the north star's multi-GPU target (256
         # tables split over the N GPUs, strong scaling), its own clock
         if not args.no_compaction_strong:

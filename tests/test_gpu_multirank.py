@@ -179,7 +179,7 @@ def test_rccl_world1_collectives():
 
 
 def test_bench_line_two_ranks_one_gpu(tmp_path):
-    """bench.py's whole N > 1 default line -- the headline, compaction_strong,
+    """bench.py's whole N > 1 --full line -- the headline, compaction_strong,
     headline_with_reader and the probe / varlen sub-records -- as two ranks on
     cuda:0 over gloo (torch.distributed.run, 127.0.0.1): it runs to the end
     and rank 0's JSON line carries every record with its parity, so the
@@ -191,7 +191,7 @@ def test_bench_line_two_ranks_one_gpu(tmp_path):
     env = dict(os.environ, ADL_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--no-cpu-baseline", "--no-e2e"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]

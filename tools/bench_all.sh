@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 : > gpurun_out/bench_all.jsonl
 for wl in ${WORKLOADS:-single varlen compaction probe}; do
-  timeout -k 10 600 python3 bench.py --steps ${STEPS:-20} --warmup 3 --workload $wl ${BENCH_ARGS:-} \
+  timeout -k 10 600 python3 bench.py --full --steps ${STEPS:-20} --warmup 3 --workload $wl ${BENCH_ARGS:-} \
     > gpurun_out/bench_$wl.log 2>&1
   rc=$?
   echo "=== $wl rc=$rc"

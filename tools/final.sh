@@ -17,7 +17,7 @@ if [ "${SKIP_PMC:-0}" != 1 ]; then
   bash tools/pmc_all.sh "$OUT/pmc" ${PMC_WORKLOADS:-single varlen compaction probe} > "$OUT/pmc.log" 2>&1 || { tail -5 "$OUT/pmc.log"; exit 1; }
   if [ "${PMC_ONLY:-0}" = 1 ]; then
     step bench_default
-    timeout -k 10 600 python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
+    timeout -k 10 600 python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
     tail -c 400 "$OUT/bench_default.json"
     exit 0
   fi
@@ -42,14 +42,14 @@ bash tools/bench_all.sh || exit 1
 cp gpurun_out/bench_all.jsonl "$OUT/bench_all.jsonl"
 step rocprof
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-compaction-strong --no-sub-records --no-reader > "$OUT/prof_bench.json" 2> "$OUT/prof.err" || exit 1
+  python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-compaction-strong --no-sub-records --no-reader > "$OUT/prof_bench.json" 2> "$OUT/prof.err" || exit 1
 step rocprof_varlen
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_varlen" -o run --output-format csv -- \
-  python3 bench.py --steps 20 --warmup 5 --workload varlen --no-cpu-baseline --no-e2e > "$OUT/prof_varlen_bench.json" 2> "$OUT/prof_varlen.err" || exit 1
+  python3 bench.py --full --steps 20 --warmup 5 --workload varlen --no-cpu-baseline --no-e2e > "$OUT/prof_varlen_bench.json" 2> "$OUT/prof_varlen.err" || exit 1
 step rocprof_probe
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_probe" -o run --output-format csv -- \
-  python3 bench.py --steps 5 --warmup 2 --workload probe --no-cpu-baseline --no-e2e > "$OUT/prof_probe_bench.json" 2> "$OUT/prof_probe.err" || exit 1
+  python3 bench.py --full --steps 5 --warmup 2 --workload probe --no-cpu-baseline --no-e2e > "$OUT/prof_probe_bench.json" 2> "$OUT/prof_probe.err" || exit 1
 step bench_default
-timeout -k 10 600 python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
+timeout -k 10 600 python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
 tail -c 400 "$OUT/bench_default.json"
 exit 0

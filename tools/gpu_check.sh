@@ -25,9 +25,9 @@ step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
 step pytest_gpu ${PYTEST_SECS:-900} python -m pytest tests -m gpu -q -rf ${PYTEST_ARGS:-}
 rc=$?; ok_or_testfail $rc || exit $rc
 [ "${SKIP_BENCH:-0}" = 1 ] && exit 0
-step bench 600 python bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} || exit $?
+step bench 600 python bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-} || exit $?
 cat "$OUT/bench.log" | grep '^{' > "$OUT/bench.json" || true
 step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e || exit $?
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e || exit $?
 find "$OUT/prof" -name "*kernel_stats.csv" | head -5
 exit 0

@@ -36,14 +36,14 @@ if [ -n "${PYTEST:-}" ]; then
   step pytest 900 python -u -m pytest $PYTEST -m gpu -x -q --timeout 300 --timeout-method thread -rf || exit $?
 fi
 if [ "${BENCH:-0}" = 1 ]; then
-  step bench 600 python bench.py ${BENCH_ARGS:-} || exit $?
+  step bench 600 python bench.py --full ${BENCH_ARGS:-} || exit $?
   grep '^{' "$OUT/bench.log" > "$OUT/bench.json" || true
 fi
 if [ -n "${AB_PROBE:-}" ]; then
   for rep in $(seq 1 $AB_PROBE); do
     for lib in abl/base/libadlbloom.so adlsm-tree_amd/lib/libadlbloom.so; do
       n=$(basename $(dirname $lib))
-      ADL_BLOOM_LIB=$lib step ab_probe_${n}_$rep 300 python bench.py --workload probe --steps 20 --warmup 3 \
+      ADL_BLOOM_LIB=$lib step ab_probe_${n}_$rep 300 python bench.py --full --workload probe --steps 20 --warmup 3 \
         --no-cpu-baseline --no-e2e || exit $?
     done
   done
@@ -56,7 +56,7 @@ if [ "${PROF_PROBE:-0}" = 1 ]; then
   for lib in abl/base/libadlbloom.so adlsm-tree_amd/lib/libadlbloom.so; do
     n=$(basename $(dirname $lib))
     ADL_BLOOM_LIB=$lib step prof_probe_$n 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_probe_$n" -o run \
-      --output-format csv -- python3 bench.py --workload probe --steps 10 --warmup 2 --no-cpu-baseline --no-e2e \
+      --output-format csv -- python3 bench.py --full --workload probe --steps 10 --warmup 2 --no-cpu-baseline --no-e2e \
       || exit $?
     python3 tools/kstats_pb.py "$OUT/prof_probe_$n" | tee -a "$OUT/prof_probe.txt"
   done
