@@ -1612,6 +1612,10 @@ int launch_binned_dt(const Plan &p, Keys keys, uint8_t *d_bitmaps, void *ws, hip
     ft.tile_f = (cptr<uint32_t>)tile_f;
     ft.sc_f = (cptr<uint32_t>)sc_f;
   }
+  // what ran, for the ADL_BLOOM_DEBUG line below: only bloom_bin16_kernel has
+  // a work-queue form, so the generic pass A is static whatever dyn_a says
+  const char *a_kernel = p.total_chunks ? "generic bloom_bin_kernel" : "none";
+  bool a_queued = false;
   hipEvent_t *ev = prof_slot();
   if (ev && !p.total_chunks) {  // no pass A: an empty interval
     ADL_HIP_TRY(hipEventRecord(ev[0], st));
@@ -1639,6 +1643,9 @@ int launch_binned_dt(const Plan &p, Keys keys, uint8_t *d_bitmaps, void *ws, hip
     // queues or in the static order
     auto bin16 = [&](auto src, BuildArgs args, bool hashed) -> int {
       using S = decltype(src);
+      a_queued = dyn_a;
+      a_kernel = hashed ? (p.claim ? "bin16 SrcH claim" : "bin16 SrcH dense")
+                        : (p.claim ? "bin16 Src16 claim" : "bin16 Src16 dense");
       if (p.claim) {
         args.claim = claim_used = 1;
         if (dyn_a)
@@ -1682,6 +1689,9 @@ int launch_binned_dt(const Plan &p, Keys keys, uint8_t *d_bitmaps, void *ws, hip
   BuildArgs ab = aa;
   ab.claim = claim_used;
   t_last_claim = claim_used != 0;
+  if (kn.debug)
+    fprintf(stderr, "adl_bloom launch: pass A %s (%s, %s), pass B %s (%u per CU, %s)\n", a_queued ? "queued" : "static",
+            a_kernel, DT ? "DT" : "kernarg", dyn_b ? "queued" : "static", p.occ_b, DT ? "DT" : "kernarg");
   auto go_b = [&](auto lim, auto kern) -> int {
     if (int rc = lim()) return rc;
     hipExtLaunchKernelGGL(kern, dim3(p.grid_b), dim3(kBlockB), p.lds_b, st, ev ? ev[2] : nullptr,

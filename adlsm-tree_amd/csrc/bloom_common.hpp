@@ -3,8 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <vector>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -387,6 +389,15 @@ inline hipStream_t sync_stream(void *stream) { return stream ? (hipStream_t)stre
 // Small host -> device uploads in stream order from pinned memory (a build's
 // filter descriptors): a ring of slots per thread, each reused only after its
 // previous copy has completed.
+//
+// An outgrown slot buffer is kept until the thread ends, not freed where it
+// is replaced: hipHostFree waits for every stream of the device, and so for a
+// resident probe server's kernel (probe_server.hip).  A build beside Gets
+// whose descriptors outgrew a slot stood still there until the server's kernel
+// and its queued successor had idled out or reached their life limits
+// (tests/test_gpu_claim.py, test_build_queue_selection_default_mode: 120 s
+// when it ran with the idle limit at 60 s).  A slot at least doubles, so the buffers it has
+// retired add up to less than the one in use.
 struct UploadRing {
   static constexpr int kSlots = 4;
   uint8_t *host[kSlots] = {};
@@ -394,12 +405,14 @@ struct UploadRing {
   hipEvent_t ev[kSlots] = {};
   bool used[kSlots] = {};
   int next = 0;
+  std::vector<uint8_t *> retired;
   ~UploadRing() {
     for (int s = 0; s < kSlots; ++s) {
       if (used[s]) (void)hipEventSynchronize(ev[s]);
       if (ev[s]) (void)hipEventDestroy(ev[s]);
       if (host[s]) (void)hipHostFree(host[s]);
     }
+    for (uint8_t *h : retired) (void)hipHostFree(h);
   }
   int upload(void *dst, const void *src, uint64_t bytes, hipStream_t st) {
     const int s = next;
@@ -408,10 +421,10 @@ struct UploadRing {
     if (used[s]) ADL_HIP_TRY(hipEventSynchronize(ev[s]));
     used[s] = false;
     if (bytes > cap[s]) {
-      if (host[s]) (void)hipHostFree(host[s]);
+      if (host[s]) retired.push_back(host[s]);  // (its last copy has completed: the event above)
       host[s] = nullptr;
+      const uint64_t want = round_up(std::max(bytes, 2 * cap[s]), 1 << 16);
       cap[s] = 0;
-      const uint64_t want = round_up(bytes, 1 << 16);
       ADL_HIP_TRY(hipHostMalloc((void **)&host[s], want, hipHostMallocDefault));
       cap[s] = want;
     }

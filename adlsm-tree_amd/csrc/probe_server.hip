@@ -87,9 +87,16 @@ constexpr uint32_t kInlineBit = 0x80000000u;  // in a bell: the request is in th
 // In a bell: the cache arena changed since the server last dropped its
 // cached copies of it (a put published a block): the wave invalidates its
 // caches (a system-scope acquire) before it reads any filter bits of that
-// poll.  Round 5 did so after every poll that found a request, which dropped
-// the L2 of the server's XCD under a co-running build ~100 000 times a second
-// (pass B 10 % slower beside Gets, profiles/r06/).
+// poll.  Round 5 did so after every poll that found a request, which drops
+// the L2 lines of the server's XCD ~100 000 times a second under a co-running
+// build and was suspected of slowing its pass B.  The A/B of the two forms
+// measured the same build times beside Gets (headline pass B 0.0746 ms
+// on-put against 0.0753 always, compaction pass B 1.5543 against 1.5547:
+// profiles/r06/check/coexist_server_invalidate_{on_put,always}.json), so
+// on-put saves the acquires but buys no build time;
+// ADL_BLOOM_SERVER_INVALIDATE=1 keeps round 5's form.  Both are tested with
+// one kernel resident across a reused arena range
+// (tests/test_gpu_readpath.py, test_probe_server_gets_after_arena_range_reuse).
 constexpr uint32_t kInvalidateBit = 0x40000000u;
 constexpr uint32_t kSeqMask = 0x3FFFFFFFu;
 constexpr uint32_t kLineCheck = 0x5EED5EEDu;  // the XOR of line_word_hash over a line's 16 words

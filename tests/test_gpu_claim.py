@@ -12,6 +12,7 @@ equal BloomFilter::Keys2Block (reference src/filter_block.cpp:9-33).
 """
 import hashlib
 import random
+import re
 
 import numpy as np
 import pytest
@@ -169,13 +170,34 @@ def test_claim_positions_count(dev, ab, oracle, claim, knobs):
         assert np.array_equal(out[o:o + int(sb.sizes[f])], oracle.keys2block(hk[kb[f]:kb[f + 1]])), f
 
 
-def test_builds_with_a_resident_server(dev, ab, oracle, golden):
-    """While a resident probe server exists (a reader), pass A and pass B take
-    their chunks and tiles from the work queues (GroupQueue, bloom_build.hip)
-    instead of the static stripes.  The same bitmaps: the 10 M reference SHA
-    (chunk/table layout), 256 x 10 K (claim layout), 32 x 100 K (two pass-B
-    workgroups per CU), var-len keys, built while single-key Gets keep the
-    server running."""
+LAUNCH = re.compile(r"adl_bloom launch: pass A (queued|static) \((.+?), (DT|kernarg)\), "
+                    r"pass B (queued|static) \((\d) per CU, (DT|kernarg)\)")
+
+
+def _launches(capfd):
+    """(A order, A kernel, A descriptors, B order, B per CU, B descriptors) of
+    every launch pair since the last call (the ADL_BLOOM_DEBUG launch line)."""
+    return [m.groups() for m in LAUNCH.finditer(capfd.readouterr().err)]
+
+
+def test_builds_with_a_resident_server(dev, ab, oracle, golden, knobs, capfd):
+    """While a probe server object exists (a reader) and
+    ADL_BLOOM_BUILD_QUEUES=1, pass A and pass B take their chunks and tiles
+    from the work queues (GroupQueue, bloom_build.hip) instead of the static
+    stripes: the launch line of every build says so.  (The default, 2, queues
+    only while the server's kernel is resident and a pass has many items per
+    workgroup, which keeps pass A of every shape here static:
+    test_build_queue_selection_default_mode.)  The same bitmaps: the 10 M
+    reference SHA (chunk/table layout), 256 x 10 K (claim layout), 32 x 100 K
+    (two pass-B workgroups per CU), var-len keys, built while single-key Gets
+    keep the server running."""
+    knobs.set("ADL_BLOOM_BUILD_QUEUES", "1")
+    knobs.set("ADL_BLOOM_DEBUG", "1")
+
+    def queued(kernel, occ, dt):
+        d = "DT" if dt else "kernarg"
+        return ("queued", kernel, d, "queued", str(occ), d)
+
     blk_keys = oracle.splitmix_keys16(0x5151, 20_000)
     bm0 = oracle.keys2block(blk_keys)
     cache = ab.FilterCache(8 << 20, max_tables=8)
@@ -194,14 +216,20 @@ def test_builds_with_a_resident_server(dev, ab, oracle, golden):
         b = ab.Builder(g["n"], 10)
         for r in range(3):
             get(r + 1)
+            capfd.readouterr()
             bm = b.build(keys).cpu().numpy()
+            assert _launches(capfd) == [queued("bin16 Src16 dense", 1, False)], r
             assert hashlib.sha256(bm.tobytes()).hexdigest() == g["sha256"], r
         del keys, b
-        for sizes in ([10_000] * 256, [100_000] * 32, [1, 0, 70_000, 5]):
+        for sizes, line in (([10_000] * 256, queued("bin16 Src16 claim", 2, True)),
+                            ([100_000] * 32, queued("bin16 Src16 dense", 2, True)),
+                            ([1, 0, 70_000, 5], queued("bin16 Src16 dense", 1, False))):
             get(7)
+            capfd.readouterr()
             kb = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
             hk = oracle.splitmix_keys16(0xAB + len(sizes), int(kb[-1]))
             out, boff, nbytes = ab.build_segmented(dev.from_numpy(hk).cuda(), kb)
+            assert _launches(capfd) == [line], len(sizes)
             out = out.cpu().numpy()
             for f in range(len(sizes)):
                 if sizes[f]:
@@ -209,7 +237,62 @@ def test_builds_with_a_resident_server(dev, ab, oracle, golden):
                                           oracle.keys2block(hk[int(kb[f]):int(kb[f + 1])])), (len(sizes), f)
         data, offs = ab.synth_varlen(300_000, seed=5)
         get(9)
+        capfd.readouterr()
         got = ab.build(data, offs).cpu().numpy()
+        assert _launches(capfd) == [queued("bin16 SrcH dense", 1, False)]
         assert np.array_equal(got, oracle.keys2block(data.cpu().numpy(), offs.cpu().numpy().view(np.uint64)))
     finally:
         cache.close()
+
+
+def test_build_queue_selection_default_mode(dev, ab, oracle, knobs, capfd):
+    """ADL_BLOOM_BUILD_QUEUES at its default (2): a pass queues only while a
+    probe server's kernel is resident, and then only with at least 16 items
+    per workgroup (pass B also when two of its workgroups share a CU).  256
+    CUs: 4096 x 300 keys is 4096 chunks, 16 per pass-A workgroup, and two
+    pass-B workgroups per CU; 4095 x 300 is one chunk short; 1 x 100 000 is
+    256 chunks and 977 tiles for 256 workgroups of each pass.  With the cache
+    closed (no server) the first shape keeps the static order.
+
+    Four small builds of 9 filters first take every slot of the pinned ring
+    that uploads a build's filter descriptors, so the 4096-filter build has to
+    replace a slot's buffer while the server's kernel is resident.  That used
+    to free the old buffer there, which waits for every stream of the device:
+    the build stood still until the server's kernel and its queued successor
+    had idled out, and the next build then found no server (pass B static)."""
+    knobs.set("ADL_BLOOM_SERVER_IDLE_US", "5000000")  # the server stays resident between the Get and the builds
+    knobs.set("ADL_BLOOM_SERVER_LIFE_US", "600000000")
+    knobs.set("ADL_BLOOM_DEBUG", "1")
+    blk_keys = oracle.splitmix_keys16(0x5152, 2000)
+    cache = ab.FilterCache(1 << 20, max_tables=2)
+    cache.put(b"t0", oracle.filter_block_final([oracle.keys2block(blk_keys).tobytes()], bits_per_key=10))
+
+    def build(sizes):
+        kb = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+        hk = oracle.splitmix_keys16(0xD0 + len(sizes), int(kb[-1]))
+        capfd.readouterr()
+        out, boff, nbytes = ab.build_segmented(dev.from_numpy(hk).cuda(), kb)
+        lines = _launches(capfd)
+        out = out.cpu().numpy()
+        for f in range(len(sizes)):
+            assert np.array_equal(out[int(boff[f]):int(boff[f]) + int(nbytes[f])],
+                                  oracle.keys2block(hk[int(kb[f]):int(kb[f + 1])])), (len(sizes), f)
+        assert len(lines) == 1
+        return lines[0]
+
+    for _ in range(4):
+        assert build([10] * 9)[2] == "DT"
+    before = ab.probe_server_launches()
+    try:
+        got, _ = cache.probe([b"t0"], np.zeros(1, np.uint32), blk_keys[:1])
+        assert got[0] == 1  # answered: the server's kernel is resident
+        assert build([300] * 4096) == ("queued", "bin16 Src16 claim", "DT", "queued", "2", "DT")
+        assert build([300] * 4095) == ("static", "bin16 Src16 claim", "DT", "queued", "2", "DT")
+        assert build([100_000]) == ("static", "bin16 Src16 dense", "kernarg", "static", "1", "kernarg")
+        # the same kernel all along: it and at most the successor that the
+        # launcher thread queues behind it (counted when queued; it starts
+        # only when the first one ends)
+        assert 1 <= ab.probe_server_launches() - before <= 2
+    finally:
+        cache.close()
+    assert build([300] * 4096) == ("static", "bin16 Src16 claim", "DT", "static", "2", "DT")

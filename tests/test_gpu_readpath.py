@@ -455,6 +455,85 @@ def test_probe_server_threads(dev, ab, oracle):
     assert sorted(big_ms)[len(big_ms) // 2] < 15.0, big_ms
 
 
+@pytest.mark.parametrize("invalidate", [None, "1"], ids=["on-put", "always"])
+def test_probe_server_gets_after_arena_range_reuse(dev, ab, oracle, knobs, invalidate):
+    """Server-only Gets of a block put into an arena range that another block
+    just left, with ONE server kernel resident throughout (idle and life limits
+    raised; adl_bloom_probe_server_launches() does not move), so no kernel
+    dispatch invalidates anything on the way: what keeps the wave from
+    answering out of a cached copy of the old block is its own acquire, made
+    when a bell carries the invalidate bit (probe_server.hip; by default only
+    on the first request after a put, ADL_BLOOM_SERVER_INVALIDATE=1 on every
+    request).  The allocator is first-fit (filter_cache.hip, alloc), so a
+    block put after a remove of an equally large one takes its range.
+
+    The two one-filter blocks are 64 KiB bitmaps made by hand: all 0x00 and
+    all 0xFF, then the reverse, then random bytes and their complement.  B
+    differs from A in every bit, so a line served from a stale copy answers
+    wrongly whichever block it is stale from.  4000 fixed keys x 6 positions
+    over 512 lines of 128 bytes: every line is read (a given line is missed
+    with probability e^-47).  Between a put and the last Get after it there
+    is no launched probe, no build and no large batch.
+
+    The launch count: the server's launcher thread queues one successor
+    kernel behind the running one soon after the first answer (it starts
+    only when the first ends, so it dispatches nothing meanwhile) and counts
+    it.  So the count is taken before the first Get and again after the first
+    block's Gets, before any range is reused: one or two launches by then,
+    and not one more until the end.  Had the first kernel ended, its successor
+    would have started and the next Get would have had a third queued."""
+    knobs.set("ADL_BLOOM_SERVER_IDLE_US", "5000000")
+    knobs.set("ADL_BLOOM_SERVER_LIFE_US", "600000000")
+    if invalidate is None:
+        knobs.unset("ADL_BLOOM_SERVER_INVALIDATE")
+    else:
+        knobs.set("ADL_BLOOM_SERVER_INVALIDATE", invalidate)
+    nbytes = 64 << 10
+    q = oracle.splitmix_keys16(0x57A1E, 4000)
+    rnd = np.random.default_rng(0x57A1E).integers(0, 256, nbytes, dtype=np.uint8)
+    rounds = [(np.zeros(nbytes, np.uint8), np.full(nbytes, 0xFF, np.uint8)),
+              (np.full(nbytes, 0xFF, np.uint8), np.zeros(nbytes, np.uint8)),
+              (rnd, ~rnd)]
+    # batches of 2..8 over the same keys: [0:2], [2:5], [5:9], ...
+    cuts, i = [], 0
+    while i < len(q):
+        m = 2 + len(cuts) % 7
+        cuts.append((i, min(i + m, len(q))))
+        i += m
+    t1 = np.zeros(1, np.uint32)
+    t8 = np.zeros(8, np.uint32)
+    cache = ab.FilterCache(1 << 20, max_tables=4)  # room for several 64 KiB blocks
+    before = ab.probe_server_launches()
+    launches = None
+    try:
+        for r, (bm_a, bm_b) in enumerate(rounds):
+            blocks = [oracle.filter_block_final([bm.tobytes()], 10) for bm in (bm_a, bm_b)]
+            wants = [oracle.probe(q, bm) for bm in (bm_a, bm_b)]
+            if r == 2:
+                assert 0 < int(wants[0].sum()) < len(q) and 0 < int(wants[1].sum()) < len(q)
+            oid = None
+            for cycle in range(4):  # A, B, A, B: each put lands where the last block was
+                which = cycle % 2
+                if oid is not None:
+                    assert cache.remove(oid)
+                oid = b"reuse-%d-%d" % (r, cycle)
+                cache.put(oid, blocks[which])
+                want = wants[which]
+                for i in range(len(q)):
+                    got, unc = cache.probe([oid], t1, q[i:i + 1])
+                    assert unc == 0 and got[0] == want[i], (r, cycle, "single", i)
+                for a, b in cuts:
+                    got, unc = cache.probe([oid], t8[:b - a], q[a:b])
+                    assert unc == 0 and np.array_equal(got, want[a:b]), (r, cycle, "batch", a)
+                if launches is None:
+                    launches = ab.probe_server_launches()  # answered Gets, no range reused yet
+                    assert 1 <= launches - before <= 2, "the first kernel and at most its queued successor"
+            assert cache.remove(oid)
+        assert ab.probe_server_launches() == launches, "the server kernel was relaunched: the test proved nothing"
+    finally:
+        cache.close()
+
+
 def _readpath_json(args, timeout=300, **env):
     import json
 
