@@ -47,7 +47,7 @@ EXPORTS = (
     "adl_bloom_profile_each", "adl_bloom_probe_batch_workspace_bytes", "adl_bloom_probe_batch_device",
     "adl_bloom_test_fault", "adl_bloom_build_positions", "adl_bloom_get_device", "adl_bloom_set_device",
     "adl_bloom_reload_knobs", "adl_bloom_build_segmented_ex", "adl_bloom_probe_server_launches",
-    "adl_bloom_probe_server_phases",
+    "adl_bloom_probe_server_phases", "adl_bloom_probe_fanout_device", "adl_bloom_filter_cache_probe_fanout",
 )
 
 _LIB = None
@@ -94,6 +94,9 @@ def lib() -> ctypes.CDLL:
         "adl_bloom_filter_cache_stats": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(u64)]),
         "adl_bloom_filter_cache_probe": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_char_p), vp, u32, u32, vp, vp,
                                                          u64, u32, vp, vp, ctypes.POINTER(u64), vp]),
+        "adl_bloom_filter_cache_probe_fanout": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_char_p), vp, u32, u32, vp,
+                                                                vp, u64, u32, vp, vp, vp, ctypes.POINTER(u64), vp]),
+        "adl_bloom_probe_fanout_device": (ctypes.c_int, [vp, vp, u64, u32, vp, vp, u64, u32, vp, vp, vp, i32, vp, vp]),
         "adl_bloom_probe_device": (ctypes.c_int, [vp, vp, u64, u32, i32, vp, u64, vp, vp]),
         "adl_bloom_probe_batch_workspace_bytes": (u64, [u64, u32, i32, u32]),
         "adl_bloom_probe_batch_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, i32, vp, vp, u64, vp]),
@@ -367,6 +370,21 @@ def probe_multi(keys, filter_id, bitmaps, bitmap_off, offsets=None, bits_per_key
     return out[:n]
 
 
+def probe_fanout(keys, pair_begin, pair_filter, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10, stream=None):
+    """Key i against each filter pair_filter[pair_begin[i]:pair_begin[i+1]] (device int32 tensors read as
+    uint32: pair_begin has n+1 entries and starts at 0); one answer per pair, in pair order -- probe_multi
+    on the expanded pairs, with every key hashed once.  bitmap_off: device uint64 tensor (F+1)."""
+    pk, po, n, stride = _keyset(keys, offsets)
+    assert pair_begin.numel() == n + 1, "pair_begin: one entry per key and one more"
+    npairs = pair_filter.numel()
+    out = _torch().empty(max(npairs, 1), dtype=_torch().uint8, device=keys.device)
+    _check(lib().adl_bloom_probe_fanout_device(pk, po, n, stride, _dptr(pair_begin), _dptr(pair_filter), npairs,
+                                               bitmap_off.numel() - 1, _dptr(bitmaps), _dptr(bitmap_off), None,
+                                               bits_per_key, _dptr(out), _stream(stream)),
+           "adl_bloom_probe_fanout_device")
+    return out[:npairs]
+
+
 def probe_batch(keys, filter_id, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10, stream=None,
                 bitmap_end=None, out=None):
     """Large-batch multi-filter probe (adl_bloom_probe_batch_device): the answers of
@@ -565,6 +583,33 @@ class FilterCache:
                                                   out.ctypes.data, ctypes.byref(unc), None),
                "adl_bloom_filter_cache_probe")
         return out[:n], unc.value
+
+    def probe_fanout(self, oids, pair_begin, pair_table, keys: np.ndarray, offsets=None, filter: int = 0):
+        """Key i against filter `filter` of every table oids[t], t in pair_table[pair_begin[i]:pair_begin[i+1]];
+        returns (0/1 per pair in pair order, uncached pair count): probe() on the expanded pairs, each key
+        uploaded and hashed once."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        if offsets is None:
+            n, stride, po = keys.shape[0], keys.shape[1], None
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n, stride, po = len(offsets) - 1, 0, offsets.ctypes.data
+        arr = (ctypes.c_char_p * max(len(oids), 1))(*oids)
+        lens = np.array([len(o) for o in oids] or [0], dtype=np.uint64)
+        pb = np.ascontiguousarray(pair_begin, dtype=np.uint32)
+        tab = np.ascontiguousarray(pair_table, dtype=np.uint32)
+        if len(pb) != n + 1:
+            raise ValueError("pair_begin needs one entry per key and one more")
+        if len(pb) and int(pb[-1]) != len(tab):
+            raise ValueError("pair_begin[-1] must equal len(pair_table)")
+        out = np.empty(max(len(tab), 1), dtype=np.uint8)
+        unc = ctypes.c_uint64()
+        kp = keys.ctypes.data if keys.size else np.zeros(1, np.uint8).ctypes.data
+        _check(lib().adl_bloom_filter_cache_probe_fanout(self._h, arr, lens.ctypes.data, len(oids), filter, kp, po,
+                                                         n, stride, pb.ctypes.data, tab.ctypes.data, out.ctypes.data,
+                                                         ctypes.byref(unc), None),
+               "adl_bloom_filter_cache_probe_fanout")
+        return out[:len(tab)], unc.value
 
     def close(self):
         if self._h:

@@ -460,6 +460,13 @@ __attribute__((visibility("hidden"))) int adl_probe_ranges_device_ev(
     uint32_t num_filters, const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end,
     const uint8_t *d_k, uint8_t *d_out, hipStream_t st, hipEvent_t done);
 
+// The same for adl_bloom_probe_fanout_device (d_k[f]: filter f's probe count).
+__attribute__((visibility("hidden"))) int adl_probe_fanout_device_ev(
+    const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys, uint32_t key_stride,
+    const uint32_t *d_pair_begin, const uint32_t *d_pair_filter, uint64_t num_pairs, uint32_t num_filters,
+    const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end, const uint8_t *d_k, uint8_t *d_out,
+    hipStream_t st, hipEvent_t done);
+
 // adl_bloom_test_fault's armed sites (-1: off).  take() disarms and returns the
 // argument, so an armed fault fires once.
 struct TestFaults {

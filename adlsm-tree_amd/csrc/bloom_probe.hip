@@ -64,6 +64,45 @@ struct ModLds {
   uint32_t magic, shift_k;  // shift | k << 8
 };
 
+// The workgroup's share of building the table (nf <= kLdsFilters); a barrier
+// must follow before filter_lookup reads it.
+__device__ __forceinline__ void mod_table_fill(ModLds *lmod, uint32_t nf, uint32_t k,
+                                               const uint8_t *__restrict__ kf,
+                                               const uint64_t *__restrict__ boff,
+                                               const uint64_t *__restrict__ bend) {
+  for (uint32_t f = threadIdx.x; f < nf; f += kBlockP) {
+    // an empty range (m = 0: a filter the table does not have) and a filter
+    // of 2^31 bits or more answer 0 below and need no divisor
+    const uint64_t bytes = (bend ? bend[f] : boff[f + 1]) - boff[f];
+    const uint32_t m = bytes <= 0x0fffffffull ? (uint32_t)(bytes * 8) : 0u;
+    const FastMod fm = m ? fastmod_for(m) : FastMod{};
+    lmod[f] = ModLds{fm.magic, fm.shift | (kf ? (uint32_t)kf[f] : k) << 8};
+  }
+}
+
+// Filter f's bitmap start, divisor and probe count.  false: the query answers
+// 0 (f >= nf, an empty filter, or one of 2^31 bits or more, outside the
+// reference's int m, src/filter_block.cpp:50).
+__device__ __forceinline__ bool filter_lookup(uint32_t f, uint32_t nf, bool lds_tab, const ModLds *lmod, uint32_t k,
+                                              const uint8_t *__restrict__ kf, const uint64_t *__restrict__ boff,
+                                              const uint64_t *__restrict__ bend, uint64_t &b0, FastMod &mod,
+                                              uint32_t &kq) {
+  if (f >= nf) return false;
+  b0 = boff[f];
+  const uint64_t b1 = bend ? bend[f] : boff[f + 1];
+  const uint32_t m = b1 - b0 <= 0x0fffffffull ? (uint32_t)((b1 - b0) * 8) : 0u;
+  if (m == 0) return false;
+  if (lds_tab) {
+    const ModLds e = lmod[f];
+    mod = FastMod{m, e.magic, e.shift_k & 0xFFu, 0u};
+    kq = e.shift_k >> 8;
+  } else {
+    mod = fastmod_for(m);
+    kq = kf ? (uint32_t)kf[f] : k;
+  }
+  return true;
+}
+
 template <class Keys>
 __global__ __launch_bounds__(kBlockP) void bloom_probe_multi_kernel(
     Keys keys, uint64_t n, uint32_t k, const uint8_t *__restrict__ kf, const uint32_t *__restrict__ fid,
@@ -73,42 +112,84 @@ __global__ __launch_bounds__(kBlockP) void bloom_probe_multi_kernel(
   extern __shared__ ModLds lmod[];
   const bool lds_tab = nf <= kLdsFilters;
   if (lds_tab) {
-    for (uint32_t f = threadIdx.x; f < nf; f += kBlockP) {
-      // an empty range (m = 0: a filter the table does not have) and a filter
-      // of 2^31 bits or more answer 0 below and need no divisor
-      const uint64_t bytes = (bend ? bend[f] : boff[f + 1]) - boff[f];
-      const uint32_t m = bytes <= 0x0fffffffull ? (uint32_t)(bytes * 8) : 0u;
-      const FastMod fm = m ? fastmod_for(m) : FastMod{};
-      lmod[f] = ModLds{fm.magic, fm.shift | (kf ? (uint32_t)kf[f] : k) << 8};
-    }
+    mod_table_fill(lmod, nf, k, kf, boff, bend);
     __syncthreads();
   }
   for (uint64_t i = blockIdx.x * (uint64_t)kBlockP + threadIdx.x; i < n;
        i += (uint64_t)gridDim.x * kBlockP) {
     const uint32_t f = fid ? fid[i] : uniform_f;  // fid == nullptr: every query -> uniform_f
     uint8_t hit = 0;
-    if (f < nf) {
-      const uint64_t b0 = boff[f], b1 = bend ? bend[f] : boff[f + 1];
-      // 0 for an empty filter or one of 2^31 bits or more (outside the
-      // reference's int m, src/filter_block.cpp:50)
-      const uint32_t m = b1 - b0 <= 0x0fffffffull ? (uint32_t)((b1 - b0) * 8) : 0u;
-      if (m != 0) {
-        FastMod mod;
-        uint32_t kq;
-        if (lds_tab) {
-          const ModLds e = lmod[f];
-          mod = FastMod{m, e.magic, e.shift_k & 0xFFu, 0u};
-          kq = e.shift_k >> 8;
-        } else {
-          mod = fastmod_for(m);
-          kq = kf ? (uint32_t)kf[f] : k;
-        }
-        uint32_t h1, h2;
-        keys.hash(i, h1, h2);
-        hit = probe_bits(bitmaps + b0, h1, h2, kq, mod);
-      }
+    uint64_t b0;
+    FastMod mod;
+    uint32_t kq;
+    if (filter_lookup(f, nf, lds_tab, lmod, k, kf, boff, bend, b0, mod, kq)) {
+      uint32_t h1, h2;
+      keys.hash(i, h1, h2);
+      hit = probe_bits(bitmaps + b0, h1, h2, kq, mod);
     }
     out[i] = hit;
+  }
+}
+
+// Fan-out probe: key i against each filter of its own list, pair_filter
+// [pair_begin[i], pair_begin[i+1]) (CSR, pair_begin[0] = 0), out[p] per pair in
+// pair order -- Level::Get's shape (src/revision.cpp:265-310: one lookup key,
+// every table of the level whose range covers it).  The hash pair of a key is
+// the same for all its filters (only m, k and the bitmap differ), so a
+// workgroup takes 256 keys at a time, lane t hashes key kb+t ONCE into LDS,
+// and the lanes then stride over the block's pairs, one pair per lane per
+// round whatever the fan-out of single keys is: pair_filter loads and out
+// stores are coalesced, and a key with 700 candidates is spread over the
+// workgroup instead of serialising one lane.  The owner of pair p is found by
+// an upper-bound search of the block's begin entries in LDS (8 steps); keys
+// without candidates are never hashed and never found.  Every answer equals
+// bloom_probe_multi_kernel's on the expanded pairs (the same table, lookup and
+// bit reads).  np bounds the pair ids should pair_begin hold anything larger.
+template <class Keys>
+__global__ __launch_bounds__(kBlockP) void bloom_probe_fanout_kernel(
+    Keys keys, uint64_t nkeys, const uint32_t *__restrict__ pair_begin, const uint32_t *__restrict__ pair_filter,
+    uint32_t np, uint32_t k, const uint8_t *__restrict__ kf, uint32_t nf, const uint8_t *__restrict__ bitmaps,
+    const uint64_t *__restrict__ boff, const uint64_t *__restrict__ bend, uint8_t *__restrict__ out) {
+  extern __shared__ ModLds lmod[];
+  __shared__ uint32_t sh1[kBlockP], sh2[kBlockP], spb[kBlockP + 1];
+  const bool lds_tab = nf <= kLdsFilters;
+  if (lds_tab) mod_table_fill(lmod, nf, k, kf, boff, bend);  // (the first barrier below covers it)
+  const uint32_t t = threadIdx.x;
+  const uint64_t nblk = (nkeys + kBlockP - 1) / kBlockP;
+  for (uint64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const uint64_t kb = blk * kBlockP;
+    const uint32_t nk = (uint32_t)(nkeys - kb < (uint64_t)kBlockP ? nkeys - kb : (uint64_t)kBlockP);
+    if (t < nk) {
+      const uint32_t b = pair_begin[kb + t], e = pair_begin[kb + t + 1];
+      spb[t] = b;
+      if (t == nk - 1) spb[nk] = e;
+      // (hashing every key, so that the key loads need not wait for the begin
+      // entries, measured the same on 1 000-key batches)
+      if (e > b) {
+        uint32_t h1, h2;
+        keys.hash(kb + t, h1, h2);
+        sh1[t] = h1;
+        sh2[t] = h2;
+      }
+    }
+    __syncthreads();
+    const uint32_t p1 = spb[nk] < np ? spb[nk] : np;
+    for (uint64_t p = (uint64_t)spb[0] + t; p < p1; p += kBlockP) {
+      // the first j in [1, nk] with spb[j] > p (spb[nk] > p): key j - 1 owns p
+      uint32_t lo = 1, hi = nk;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (spb[mid] > (uint32_t)p) hi = mid; else lo = mid + 1;
+      }
+      uint8_t hit = 0;
+      uint64_t b0;
+      FastMod mod;
+      uint32_t kq;
+      if (filter_lookup(pair_filter[p], nf, lds_tab, lmod, k, kf, boff, bend, b0, mod, kq))
+        hit = probe_bits(bitmaps + b0, sh1[lo - 1], sh2[lo - 1], kq, mod);
+      out[p] = hit;
+    }
+    __syncthreads();  // the next block of keys reuses sh1 / sh2 / spb
   }
 }
 
@@ -286,7 +367,49 @@ int probe_multi(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n, ui
     return ADL_OK;
   });
 }
+// One workgroup per 256 keys, at most 8 per CU (the rest by grid stride).
+int probe_fanout(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys, uint32_t key_stride,
+                 const uint32_t *d_pair_begin, const uint32_t *d_pair_filter, uint64_t num_pairs,
+                 uint32_t num_filters, const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end,
+                 int32_t bits_per_key, const uint8_t *d_k, uint8_t *d_out, hipStream_t st, hipEvent_t done) {
+  if (num_keys == 0 || num_pairs == 0) return ADL_OK;
+  if (!d_keys || !d_pair_begin || !d_pair_filter || !d_out || bits_per_key < 0) return ADL_ERR_INVALID_ARG;
+  if (num_filters && (!d_bitmaps || !d_begin)) return ADL_ERR_INVALID_ARG;
+  if (!d_offsets && key_stride == 0) return ADL_ERR_INVALID_ARG;
+  if (num_pairs > 0xffffffffull) return ADL_ERR_TOO_LARGE;  // pair_begin is u32
+  const uint32_t k = (uint32_t)adl_host::num_probes(bits_per_key);
+  return dispatch_keys(d_keys, d_offsets, key_stride, [&](auto keys) -> int {
+    const size_t lds = num_filters <= kLdsFilters ? (size_t)num_filters * sizeof(ModLds) : 0;
+    hipExtLaunchKernelGGL(bloom_probe_fanout_kernel<decltype(keys)>, dim3(grid_for(num_keys, kBlockP, 8)),
+                          dim3(kBlockP), lds, st, nullptr, done, 0, keys, num_keys, d_pair_begin, d_pair_filter,
+                          (uint32_t)num_pairs, k, d_k, num_filters, d_bitmaps, d_begin, d_end, d_out);
+    ADL_HIP_TRY(hipGetLastError());
+    return ADL_OK;
+  });
+}
 }  // namespace
+
+// adl_bloom_probe_fanout_device with a probe count per filter (d_k[f]), whose
+// launch also completes `done` (the filter cache, as adl_probe_ranges_device_ev).
+int adl_host::adl_probe_fanout_device_ev(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys,
+                                         uint32_t key_stride, const uint32_t *d_pair_begin,
+                                         const uint32_t *d_pair_filter, uint64_t num_pairs, uint32_t num_filters,
+                                         const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end,
+                                         const uint8_t *d_k, uint8_t *d_out, hipStream_t st, hipEvent_t done) {
+  if (num_keys && num_pairs && num_filters && !d_k) return ADL_ERR_INVALID_ARG;
+  return probe_fanout(d_keys, d_offsets, num_keys, key_stride, d_pair_begin, d_pair_filter, num_pairs, num_filters,
+                      d_bitmaps, d_begin, d_end, 10, d_k, d_out, st, done);
+}
+
+extern "C" int adl_bloom_probe_fanout_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys,
+                                             uint32_t key_stride, const uint32_t *d_pair_begin,
+                                             const uint32_t *d_pair_filter, uint64_t num_pairs,
+                                             uint32_t num_filters, const uint8_t *d_bitmaps,
+                                             const uint64_t *d_begin, const uint64_t *d_end, int32_t bits_per_key,
+                                             uint8_t *d_out, void *stream) {
+  return probe_fanout(d_keys, d_offsets, num_keys, key_stride, d_pair_begin, d_pair_filter, num_pairs, num_filters,
+                      d_bitmaps, d_begin, d_end, bits_per_key, nullptr, d_out, (hipStream_t)stream, nullptr);
+}
 
 // adl_bloom_probe_ranges_device with a probe count per filter (d_k[f]), whose
 // launch also completes `done` (the filter cache's small batches wait on it;

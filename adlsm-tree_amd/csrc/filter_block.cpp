@@ -293,6 +293,29 @@ RC FilterCache::Probe(const vector<string_view> &oids, const vector<uint32_t> &t
   return FromStatus(st);
 }
 
+RC FilterCache::ProbeFanout(const vector<string_view> &oids, const vector<uint32_t> &begin,
+                            const vector<uint32_t> &table, const KeyArena &keys, int filter, vector<uint8_t> &out,
+                            uint64_t *uncached) {
+  out.assign(table.size(), 0);
+  if (uncached) *uncached = 0;
+  if (!h_) return status_;
+  if (begin.size() != keys.size() + 1 || begin.back() != table.size() || filter < 0) return OUT_OF_RANGE;
+  if (table.empty()) return OK;
+  vector<const char *> ptr(oids.size());
+  vector<uint64_t> len(oids.size());
+  for (size_t j = 0; j < oids.size(); ++j) {
+    ptr[j] = oids[j].data();
+    len[j] = oids[j].size();
+  }
+  uint64_t unc = 0;
+  const int st = adl_bloom_filter_cache_probe_fanout(
+      h_, ptr.data(), len.data(), (uint32_t)oids.size(), (uint32_t)filter,
+      reinterpret_cast<const uint8_t *>(keys.bytes().data()), keys.offsets().data(), keys.size(), 0, begin.data(),
+      table.data(), out.data(), &unc, nullptr);
+  if (uncached) *uncached = unc;
+  return FromStatus(st);
+}
+
 FilterCache *FilterCache::Shared(int) { return Shared(); }
 
 FilterCache *FilterCache::Shared() {

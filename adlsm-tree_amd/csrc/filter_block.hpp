@@ -167,6 +167,13 @@ class FilterCache {
    * "may be present"; *uncached counts those queries). */
   RC Probe(const vector<string_view> &oids, const vector<uint32_t> &table, const KeyArena &keys, int filter,
            vector<uint8_t> &out, uint64_t *uncached = nullptr);
+  /* The same batch with each key given once: key i against the tables
+   * oids[table[p]], p in [begin[i], begin[i+1]) (begin: keys.size() + 1
+   * entries from 0, non-decreasing; begin.back() == table.size()).  out[p]
+   * and *uncached are Probe's on the expanded pairs; the keys are uploaded
+   * and hashed once each (one launch, adl_bloom_filter_cache_probe_fanout). */
+  RC ProbeFanout(const vector<string_view> &oids, const vector<uint32_t> &begin, const vector<uint32_t> &table,
+                 const KeyArena &keys, int filter, vector<uint8_t> &out, uint64_t *uncached = nullptr);
   /* The process-wide cache FilterBlockReader::Init(string_view) keeps its
    * bitmaps in, for blocks of every bits_per_key (arena
    * ADL_BLOOM_READER_CACHE_BYTES, default 1 GiB); created on first use and

@@ -173,6 +173,89 @@ struct adl_bloom_filter_cache {
   }
 };
 
+namespace {
+
+// What a probe resolved under the cache's lock: per listed table the arena
+// range of its filter (be[j], be[num_tables + j]), whether it is cached, its
+// block's k, and the entries it pinned.  (Per-thread scratch: a single-key
+// Get allocates nothing here.)
+struct Resolved {
+  std::vector<uint64_t> be;
+  std::vector<uint8_t> cached, kt;
+  std::vector<adl_bloom_filter_cache::Iter> pinned;
+  std::string oid_key;
+};
+thread_local Resolved t_res;
+
+// Per listed table, the arena range of its filter `filter` (the all-ones
+// filter when the table is not cached, an empty range when it has no such
+// filter) and its block's k, its entry pinned and marked used.
+void resolve_tables(adl_bloom_filter_cache *c, const char *const *oids, const uint64_t *oid_lens,
+                    uint32_t num_tables, uint32_t filter, Resolved &r) {
+  r.be.assign(2 * (size_t)num_tables, 0);
+  r.cached.assign(num_tables, 0);
+  r.kt.assign(num_tables, 1);
+  r.pinned.clear();
+  std::lock_guard<std::mutex> g(c->mu);
+  for (uint32_t j = 0; j < num_tables; ++j) {
+    r.oid_key.assign(oids[j], oid_lens[j]);
+    auto it = c->index.find(r.oid_key);
+    if (it == c->index.end()) {
+      r.be[j] = 0;
+      r.be[num_tables + j] = kOnesBytes;
+      continue;
+    }
+    r.cached[j] = 1;
+    adl_bloom_filter_cache::Iter e = it->second;
+    r.kt[j] = e->k;
+    c->lru.splice(c->lru.begin(), c->lru, e);
+    ++e->pins;
+    r.pinned.push_back(e);
+    const uint64_t nf = e->off.size() - 1;
+    r.be[j] = r.be[num_tables + j] = e->base;
+    if (filter < nf) {
+      r.be[j] = e->base + e->off[filter];
+      r.be[num_tables + j] = e->base + e->off[filter + 1];
+    }
+  }
+}
+
+void unpin_tables(adl_bloom_filter_cache *c, Resolved &r) {
+  std::lock_guard<std::mutex> g(c->mu);
+  for (auto e : r.pinned) c->unpin(e);
+}
+
+// Waits for a mapped small batch by watching its n answers arrive (each is
+// written once, 0 or 1, over a 0xFF sentinel, by the probe kernel's one store
+// per query after all its reads), then for the launch's completion event.
+// true: both seen (rc may have become ADL_ERR_DEVICE); false: 2 ms passed, the
+// caller synchronizes the stream.
+bool watch_answers(const volatile uint8_t *ans, uint64_t n, hipEvent_t done, int &rc) {
+  const auto t0 = std::chrono::steady_clock::now();
+  auto late = [&] { return std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2); };
+  uint64_t i = 0;
+  for (;;) {
+    while (i < n && ans[i] != 0xff) ++i;
+    if (i == n || late()) break;
+    __builtin_ia32_pause();
+  }
+  if (i != n) return false;
+  // every answer is in: now the launch itself
+  const bool fault = adl_host::g_test_faults.take(ADL_TEST_FAULT_CACHE_COMPLETION) >= 0;
+  for (;;) {
+    const hipError_t q = fault ? hipErrorLaunchFailure : hipEventQuery(done);
+    if (q == hipSuccess) return true;
+    if (q != hipErrorNotReady) {
+      rc = ADL_ERR_DEVICE;
+      return false;
+    }
+    if (late()) return false;
+    __builtin_ia32_pause();
+  }
+}
+
+}  // namespace
+
 extern "C" {
 
 int adl_bloom_filter_cache_create(uint64_t capacity_bytes, uint32_t max_tables, int32_t bits_per_key,
@@ -319,43 +402,11 @@ int adl_bloom_filter_cache_probe(adl_bloom_filter_cache *c, const char *const *o
     //    `filter` (the all-ones filter when the table is not cached, an empty
     //    range when it has no such filter) and its block's k, its entry pinned
     //    and marked used
-    // (per-thread scratch: a single-key Get allocates nothing here)
-    thread_local std::vector<uint64_t> be;
-    thread_local std::vector<uint8_t> cached, kt;
-    thread_local std::vector<adl_bloom_filter_cache::Iter> pinned;
-    thread_local std::string oid_key;
-    be.assign(2 * (size_t)num_tables, 0);
-    cached.assign(num_tables, 0);
-    kt.assign(num_tables, 1);
-    pinned.clear();
-    {
-      std::lock_guard<std::mutex> g(c->mu);
-      for (uint32_t j = 0; j < num_tables; ++j) {
-        oid_key.assign(oids[j], oid_lens[j]);
-        auto it = c->index.find(oid_key);
-        if (it == c->index.end()) {
-          be[j] = 0;
-          be[num_tables + j] = kOnesBytes;
-          continue;
-        }
-        cached[j] = 1;
-        adl_bloom_filter_cache::Iter e = it->second;
-        kt[j] = e->k;
-        c->lru.splice(c->lru.begin(), c->lru, e);
-        ++e->pins;
-        pinned.push_back(e);
-        const uint64_t nf = e->off.size() - 1;
-        be[j] = be[num_tables + j] = e->base;
-        if (filter < nf) {
-          be[j] = e->base + e->off[filter];
-          be[num_tables + j] = e->base + e->off[filter + 1];
-        }
-      }
-    }
-    auto unpin_all = [&] {
-      std::lock_guard<std::mutex> g(c->mu);
-      for (auto e : pinned) c->unpin(e);
-    };
+    Resolved &res = t_res;
+    resolve_tables(c, oids, oid_lens, num_tables, filter, res);
+    std::vector<uint64_t> &be = res.be;
+    std::vector<uint8_t> &cached = res.cached, &kt = res.kt;
+    auto unpin_all = [&] { unpin_tables(c, res); };
     uint64_t uncached = 0;
     for (uint64_t i = 0; i < n; ++i) uncached += !cached[h_table[i]];
     // A single-key Get (up to adl_srv::kMaxQ queries): the resident server,
@@ -448,39 +499,115 @@ int adl_bloom_filter_cache_probe(adl_bloom_filter_cache *c, const char *const *o
         hipMemcpyAsync(hbuf + o_out, dbuf + o_out, n, hipMemcpyDeviceToHost, st) != hipSuccess)
       rc = ADL_ERR_DEVICE;
     // the kernel and the copies are done before any pinned range can be reused
-    bool finished = false;
-    if (done) {
-      const volatile uint8_t *ans = hbuf + o_out;
-      const auto t0 = std::chrono::steady_clock::now();
-      auto late = [&] { return std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2); };
-      uint64_t i = 0;
-      for (;;) {
-        while (i < n && ans[i] != 0xff) ++i;
-        if (i == n || late()) break;
-        __builtin_ia32_pause();
-      }
-      if (i == n) {  // every answer is in: now the launch itself
-        const bool fault = adl_host::g_test_faults.take(ADL_TEST_FAULT_CACHE_COMPLETION) >= 0;
-        for (;;) {
-          const hipError_t q = fault ? hipErrorLaunchFailure : hipEventQuery(done);
-          if (q == hipSuccess) {
-            finished = true;
-            break;
-          }
-          if (q != hipErrorNotReady) {
-            rc = ADL_ERR_DEVICE;
-            break;
-          }
-          if (late()) break;
-          __builtin_ia32_pause();
-        }
-      }
-    }
+    const bool finished = done && watch_answers(hbuf + o_out, n, done, rc);
     if (!finished && hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
     // 3. unpin (a range retired meanwhile is freed by its last unpin)
     unpin_all();
     if (rc) return rc;
     memcpy(h_out, hbuf + o_out, n);
+    if (h_uncached) *h_uncached = uncached;
+    return ADL_OK;
+  } catch (...) {
+    return ADL_ERR_OUT_OF_MEMORY;
+  }
+}
+
+int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *c, const char *const *oids, const uint64_t *oid_lens,
+                                        uint32_t num_tables, uint32_t filter, const uint8_t *h_keys,
+                                        const uint64_t *h_offsets, uint64_t num_keys, uint32_t key_stride,
+                                        const uint32_t *h_pair_begin, const uint32_t *h_pair_table, uint8_t *h_out,
+                                        uint64_t *h_uncached, void *stream) {
+  if (!c || (num_tables && (!oids || !oid_lens))) return ADL_ERR_INVALID_ARG;
+  if (h_uncached) *h_uncached = 0;
+  if (num_keys == 0) return ADL_OK;
+  if (!h_keys || !h_pair_begin || (!h_offsets && key_stride == 0)) return ADL_ERR_INVALID_ARG;
+  if (num_keys >= 0xffffffffull) return ADL_ERR_TOO_LARGE;
+  try {
+    if (h_pair_begin[0] != 0) return ADL_ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < num_keys; ++i)
+      if (h_pair_begin[i + 1] < h_pair_begin[i]) return ADL_ERR_INVALID_ARG;
+    const uint64_t np = h_pair_begin[num_keys];
+    if (np == 0) return ADL_OK;
+    if (!h_pair_table || !h_out) return ADL_ERR_INVALID_ARG;
+    for (uint64_t p = 0; p < np; ++p)
+      if (h_pair_table[p] >= num_tables) return ADL_ERR_INVALID_ARG;
+    // A Get's worth of pairs: expanded, so that the small-batch path (the
+    // resident server, the mapped buffer) serves it as before.
+    if (np <= adl_srv::kMaxQ) {
+      std::string kbytes;
+      uint64_t koff[adl_srv::kMaxQ + 1] = {0};
+      uint64_t p = 0;
+      for (uint64_t i = 0; i < num_keys && p < np; ++i) {
+        const uint64_t o0 = h_offsets ? h_offsets[i] : i * key_stride;
+        const uint64_t len = h_offsets ? h_offsets[i + 1] - o0 : key_stride;
+        for (; p < h_pair_begin[i + 1]; ++p) {
+          kbytes.append(reinterpret_cast<const char *>(h_keys) + o0, len);
+          koff[p + 1] = kbytes.size();
+        }
+      }
+      kbytes.push_back('\0');  // (a batch of empty keys still has an address)
+      return adl_bloom_filter_cache_probe(c, oids, oid_lens, num_tables, filter,
+                                          reinterpret_cast<const uint8_t *>(kbytes.data()), koff, np, 0, h_pair_table,
+                                          h_out, h_uncached, stream);
+    }
+    hipStream_t st = adl_host::sync_stream(stream);
+    // 1. under the lock: the listed tables' ranges and k, pinned and marked used
+    Resolved &res = t_res;
+    resolve_tables(c, oids, oid_lens, num_tables, filter, res);
+    uint64_t uncached = 0;
+    for (uint64_t p = 0; p < np; ++p) uncached += !res.cached[h_pair_table[p]];
+    // 2. without the lock: keys (once each), their offsets, the begin array,
+    //    the table ids and the range and k tables in one H2D, one fan-out
+    //    launch, one D2H of a byte per pair
+    const uint64_t key_bytes = h_offsets ? h_offsets[num_keys] : num_keys * (uint64_t)key_stride;
+    const uint64_t off_bytes = h_offsets ? (num_keys + 1) * 8 : 0;
+    const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
+    const uint64_t o_pb = o_offs + adl_host::round_up(off_bytes, 256);
+    const uint64_t o_pt = o_pb + adl_host::round_up((num_keys + 1) * 4, 256);
+    const uint64_t o_be = o_pt + adl_host::round_up(np * 4, 256);
+    const uint64_t o_k = o_be + adl_host::round_up(res.be.size() * 8, 256);
+    const uint64_t o_out = o_k + adl_host::round_up(num_tables, 256);
+    const uint64_t total = o_out + adl_host::round_up(np, 256);
+    // a small batch goes through the thread's mapped buffer and is waited for
+    // by watching its answers, as in adl_bloom_filter_cache_probe
+    adl_host::Staging &sg = adl_host::t_stage;
+    uint8_t *hbuf = adl_host::t_mapped.get(total), *dbuf = hbuf ? adl_host::t_mapped.dev : nullptr;
+    int rc = ADL_OK;
+    if (!hbuf) {
+      rc = sg.reserve(total, total);
+      hbuf = sg.host;
+      dbuf = sg.dev;
+    }
+    const bool spin = hbuf != sg.host && np <= 4096 && adl_host::knobs().spin;
+    if (rc == ADL_OK) {
+      if (key_bytes) memcpy(hbuf, h_keys, key_bytes);
+      if (off_bytes) memcpy(hbuf + o_offs, h_offsets, off_bytes);
+      memcpy(hbuf + o_pb, h_pair_begin, (num_keys + 1) * 4);
+      memcpy(hbuf + o_pt, h_pair_table, np * 4);
+      memcpy(hbuf + o_be, res.be.data(), res.be.size() * 8);
+      memcpy(hbuf + o_k, res.kt.data(), num_tables);
+      if (spin) memset(hbuf + o_out, 0xff, np);
+      if (hbuf == sg.host && hipMemcpyAsync(dbuf, hbuf, o_out, hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = ADL_ERR_DEVICE;
+    }
+    hipEvent_t done = spin && rc == ADL_OK ? t_done.get() : nullptr;
+    if (rc == ADL_OK) {
+      const uint64_t *d_be = reinterpret_cast<const uint64_t *>(dbuf + o_be);
+      rc = adl_host::adl_probe_fanout_device_ev(
+          dbuf, h_offsets ? reinterpret_cast<uint64_t *>(dbuf + o_offs) : nullptr, num_keys, key_stride,
+          reinterpret_cast<const uint32_t *>(dbuf + o_pb), reinterpret_cast<const uint32_t *>(dbuf + o_pt), np,
+          num_tables, c->arena, d_be, d_be + num_tables, dbuf + o_k, dbuf + o_out, st, done);
+    }
+    if (rc == ADL_OK && hbuf == sg.host &&
+        hipMemcpyAsync(hbuf + o_out, dbuf + o_out, np, hipMemcpyDeviceToHost, st) != hipSuccess)
+      rc = ADL_ERR_DEVICE;
+    // the kernel and the copies are done before any pinned range can be reused
+    const bool finished = done && watch_answers(hbuf + o_out, np, done, rc);
+    if (!finished && hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
+    // 3. unpin (a range retired meanwhile is freed by its last unpin)
+    unpin_tables(c, res);
+    if (rc) return rc;
+    memcpy(h_out, hbuf + o_out, np);
     if (h_uncached) *h_uncached = uncached;
     return ADL_OK;
   } catch (...) {

@@ -64,7 +64,11 @@ struct MultiGetFilterResult {
  * walks files_meta_ -- a set ordered by min_inner_key (FileMetaData::operator<,
  * src/file_util.hpp:163-165) iterated in reverse (src/revision.cpp:278).
  * user_keys: the batch; seq: the lookup's sequence (DB::Get reads
- * sequence_id_, src/db.cpp:168).  One cache probe for all pairs. */
+ * sequence_id_, src/db.cpp:168).  One cache probe for all pairs: each key
+ * is handed over once with its candidate list (FilterCache::ProbeFanout)
+ * where that saves upload, otherwise one query per pair (FilterCache::Probe);
+ * the answers are the same.  ADL_BLOOM_LEVEL_FANOUT=0 / 2 forces the pair /
+ * the fan-out path. */
 /* The candidate selection of LevelMultiGetFilter alone (host only): key i's
  * candidate tables are table[begin[i] .. begin[i+1]), in visiting order. */
 void LevelCandidates(const vector<TableRange> &tables, const vector<string_view> &user_keys, int64_t seq,

@@ -208,6 +208,23 @@ int adl_bloom_probe_ranges_device(const uint8_t *d_keys, const uint64_t *d_offse
                                   const uint64_t *d_begin, const uint64_t *d_end,
                                   int32_t bits_per_key, uint8_t *d_out, void *stream);
 
+/* Fan-out probe: key i against every filter of its own list, d_pair_filter
+ * [d_pair_begin[i] .. d_pair_begin[i+1]) (device arrays: num_keys+1 u32 with
+ * d_pair_begin[0] == 0, non-decreasing, d_pair_begin[num_keys] == num_pairs;
+ * num_pairs filter ids).  d_out[p] (num_pairs bytes, pair order) is what
+ * adl_bloom_probe_ranges_device answers for the pair (key i, d_pair_filter[p])
+ * -- bit for bit, including 0 for a filter id >= num_filters, an empty filter
+ * and one of 2^31 bits or more -- but each key is uploaded and hashed once
+ * for all its filters.  d_end == NULL: filter f = d_bitmaps[d_begin[f] ..
+ * d_begin[f+1]) (num_filters+1 entries).  num_keys == 0 or num_pairs == 0
+ * launches nothing.  This is Level::Get's shape (src/revision.cpp:265-310: one
+ * lookup key, every table of the level whose range covers it). */
+int adl_bloom_probe_fanout_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys,
+                                  uint32_t key_stride, const uint32_t *d_pair_begin,
+                                  const uint32_t *d_pair_filter, uint64_t num_pairs, uint32_t num_filters,
+                                  const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end,
+                                  int32_t bits_per_key, uint8_t *d_out, void *stream);
+
 /* Large-batch probe with a workspace: the answers of adl_bloom_probe_multi_device
  * (d_bitmap_end == NULL) or adl_bloom_probe_ranges_device (filter f =
  * d_bitmaps[d_bitmap_off[f] .. d_bitmap_end[f])).  For big batches of 16-byte
@@ -305,6 +322,25 @@ int adl_bloom_filter_cache_probe(adl_bloom_filter_cache *cache, const char *cons
                                  const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t n,
                                  uint32_t key_stride, const uint32_t *h_table, uint8_t *h_out,
                                  uint64_t *h_uncached, void *stream);
+
+/* The same multi-get with each key given once: key i (host keys, num_keys of
+ * them) probes filter `filter` of every table of its candidate list,
+ * h_pair_table[h_pair_begin[i] .. h_pair_begin[i+1]) (indices into the oid
+ * list; h_pair_begin: num_keys+1 u32, h_pair_begin[0] == 0, non-decreasing --
+ * anything else, or a table index >= num_tables, is ADL_ERR_INVALID_ARG).
+ * h_out[p], one byte per pair in pair order, and *h_uncached (pairs bound for
+ * tables that are not cached) are exactly what adl_bloom_filter_cache_probe
+ * gives for the expanded (key, table) pairs; the keys cross the link and are
+ * hashed once each instead of once per candidate table.  Batches of up to 8
+ * pairs are expanded and served by adl_bloom_filter_cache_probe itself (the
+ * resident server).  Synchronous.  Replaces Level::Get's loop over the
+ * level's tables (src/revision.cpp:265-310) for a batch of lookup keys. */
+int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *cache, const char *const *oids,
+                                        const uint64_t *oid_lens, uint32_t num_tables, uint32_t filter,
+                                        const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t num_keys,
+                                        uint32_t key_stride, const uint32_t *h_pair_begin,
+                                        const uint32_t *h_pair_table, uint8_t *h_out, uint64_t *h_uncached,
+                                        void *stream);
 
 /* ---------------------------------------------------------------- hash */
 
