@@ -48,6 +48,9 @@ EXPORTS = (
     "adl_bloom_test_fault", "adl_bloom_build_positions", "adl_bloom_get_device", "adl_bloom_set_device",
     "adl_bloom_reload_knobs", "adl_bloom_build_segmented_ex", "adl_bloom_probe_server_launches",
     "adl_bloom_probe_server_phases", "adl_bloom_probe_fanout_device", "adl_bloom_filter_cache_probe_fanout",
+    "adl_bloom_filter_cache_build", "adl_bloom_filter_cache_build_workspace_bytes",
+    "adl_bloom_filter_cache_build_device", "adl_bloom_filter_cache_publish", "adl_bloom_filter_cache_abandon",
+    "adl_bloom_verify_device", "adl_bloom_verify",
 )
 
 _LIB = None
@@ -97,6 +100,16 @@ def lib() -> ctypes.CDLL:
         "adl_bloom_filter_cache_probe_fanout": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_char_p), vp, u32, u32, vp,
                                                                 vp, u64, u32, vp, vp, vp, ctypes.POINTER(u64), vp]),
         "adl_bloom_probe_fanout_device": (ctypes.c_int, [vp, vp, u64, u32, vp, vp, u64, u32, vp, vp, vp, i32, vp, vp]),
+        "adl_bloom_filter_cache_build": (ctypes.c_int, [vp, vp, vp, u32, vp, u32, i32, u32, vp, u64,
+                                                         ctypes.POINTER(vp), vp]),
+        "adl_bloom_filter_cache_build_workspace_bytes": (u64, [vp, u32, i32]),
+        "adl_bloom_filter_cache_build_device": (ctypes.c_int, [vp, vp, vp, u32, vp, u32, i32, u32, vp, u64, vp, u64,
+                                                                ctypes.POINTER(vp), vp]),
+        "adl_bloom_filter_cache_publish": (ctypes.c_int, [vp, vp, ctypes.c_char_p, u64]),
+        "adl_bloom_filter_cache_abandon": (ctypes.c_int, [vp, vp]),
+        "adl_bloom_verify_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, i32, vp, vp]),
+        "adl_bloom_verify": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, i32, ctypes.POINTER(u64),
+                                             ctypes.POINTER(u64), vp]),
         "adl_bloom_probe_device": (ctypes.c_int, [vp, vp, u64, u32, i32, vp, u64, vp, vp]),
         "adl_bloom_probe_batch_workspace_bytes": (u64, [u64, u32, i32, u32]),
         "adl_bloom_probe_batch_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, i32, vp, vp, u64, vp]),
@@ -269,6 +282,7 @@ def build(keys, offsets=None, bits_per_key: int = 10, stream=None):
 
 
 SKIP_ADJACENT_DUPLICATES = 1
+CACHE_VERIFY = 2  # FilterCache.build / build_device: re-probe every build key before the block goes resident
 
 
 def build_segmented(keys, key_begin, offsets=None, bits_per_key: int = 10, stream=None, flags: int = 0):
@@ -426,6 +440,7 @@ def murmur3(seed: int, data: bytes) -> int:
 # test-only fault injection (include/adl_bloom.h, adl_bloom_test_fault)
 TEST_FAULT_PIPELINE_GROUP = 1
 TEST_FAULT_CACHE_COMPLETION = 2
+TEST_FAULT_CACHE_BUILD_CORRUPT = 3
 
 
 def test_fault(site: int, arg: int) -> None:
@@ -611,6 +626,91 @@ class FilterCache:
                "adl_bloom_filter_cache_probe_fanout")
         return out[:len(tab)], unc.value
 
+    # ---- write-through: a table's filter block built straight into the arena
+    class Ticket:
+        """A built, unpublished block (adl_bloom_cache_ticket): publish or abandon it.
+        `block`: device variant only, the host tensor the block is copied into
+        (complete once publish, abandon or a stream synchronise has returned)."""
+
+        def __init__(self, handle, keep=(), block=None, nbytes=0):
+            self._h, self._keep, self.block, self.nbytes = handle, keep, block, nbytes
+
+        def block_bytes(self) -> bytes:
+            return bytes(self.block[:self.nbytes].numpy().tobytes())
+
+    def build_status(self, keys, key_begin, offsets=None, bits_per_key: int = 10, flags: int = 0):
+        """adl_bloom_filter_cache_build on host numpy keys: (status, block bytes or None, ticket or None)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        kb = np.ascontiguousarray(key_begin, dtype=np.uint64)
+        if offsets is None:
+            stride, po = (int(keys.shape[1]) if keys.ndim == 2 else 16), None
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            stride, po = 0, offsets.ctypes.data
+        nbytes = lib().adl_bloom_filter_block_bytes(kb.ctypes.data, len(kb) - 1, bits_per_key)
+        block = np.empty(max(nbytes, 1), dtype=np.uint8)
+        kp = keys.ctypes.data if keys.size else np.zeros(16, np.uint8).ctypes.data
+        h = ctypes.c_void_p()
+        rc = lib().adl_bloom_filter_cache_build(self._h, kp, po, stride, kb.ctypes.data, len(kb) - 1, bits_per_key,
+                                                flags, block.ctypes.data, nbytes, ctypes.byref(h), None)
+        if rc != ADL_OK:
+            return rc, None, None
+        return rc, block[:nbytes].tobytes(), FilterCache.Ticket(h)
+
+    def build(self, keys, key_begin, offsets=None, bits_per_key: int = 10, flags: int = 0):
+        """Build the filter block of keys (filter f = keys [key_begin[f], key_begin[f+1])) into a reserved
+        range of the arena: returns (block: bytes, ticket).  The block is the reference's, for the file;
+        publish(ticket, oid) makes it resident under the table's oid, abandon(ticket) gives the range back."""
+        rc, block, t = self.build_status(keys, key_begin, offsets, bits_per_key, flags)
+        _check(rc, "adl_bloom_filter_cache_build")
+        return block, t
+
+    def build_device(self, keys, key_begin, offsets=None, bits_per_key: int = 10, flags: int = 0, stream=None,
+                     h_block="pinned"):
+        """The same from torch device tensors, enqueued on `stream` without a synchronise; the workspace
+        comes from torch's caching allocator and lives with the ticket.  h_block: a pinned CPU uint8 tensor
+        to receive the block, "pinned" to allocate one, or None for no download.  Returns the ticket
+        (ticket.block: that tensor)."""
+        torch = _torch()
+        kb = np.ascontiguousarray(key_begin, dtype=np.uint64)
+        L = lib()
+        nbytes = L.adl_bloom_filter_block_bytes(kb.ctypes.data, len(kb) - 1, bits_per_key)
+        wsb = L.adl_bloom_filter_cache_build_workspace_bytes(kb.ctypes.data, len(kb) - 1, bits_per_key)
+        if nbytes == 0 or wsb == 0:
+            raise AdlBloomError(-2, "filter block size")
+        ws = empty_device(wsb, keys.device if keys is not None else "cuda")
+        if isinstance(h_block, str):
+            h_block = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        stride = 0 if offsets is not None else (int(keys.shape[1]) if keys is not None else 16)
+        h = ctypes.c_void_p()
+        _check(L.adl_bloom_filter_cache_build_device(self._h, _dptr(keys), _dptr(offsets), stride, kb.ctypes.data,
+                                                     len(kb) - 1, bits_per_key, flags, _dptr(ws), wsb,
+                                                     None if h_block is None else h_block.data_ptr(),
+                                                     0 if h_block is None else h_block.numel(), ctypes.byref(h),
+                                                     _stream(stream)), "adl_bloom_filter_cache_build_device")
+        return FilterCache.Ticket(h, (ws, keys, offsets), h_block, nbytes)
+
+    def publish_status(self, ticket, oid: bytes) -> int:
+        h, ticket._h, keep = ticket._h, None, ticket._keep
+        rc = lib().adl_bloom_filter_cache_publish(self._h, h, oid, len(oid))
+        del keep  # (the build's work has ended: publish waited for it)
+        ticket._keep = ()
+        return rc
+
+    def publish(self, ticket, oid: bytes) -> None:
+        _check(self.publish_status(ticket, oid), "adl_bloom_filter_cache_publish")
+
+    def abandon(self, ticket) -> None:
+        h, ticket._h = ticket._h, None
+        _check(lib().adl_bloom_filter_cache_abandon(self._h, h), "adl_bloom_filter_cache_abandon")
+        ticket._keep = ()
+
+    def build_put(self, oid: bytes, keys, key_begin, offsets=None, bits_per_key: int = 10, flags: int = 0) -> bytes:
+        """build + publish under `oid`; returns the block."""
+        block, t = self.build(keys, key_begin, offsets, bits_per_key, flags)
+        self.publish(t, oid)
+        return block
+
     def close(self):
         if self._h:
             lib().adl_bloom_filter_cache_destroy(self._h)
@@ -621,6 +721,29 @@ class FilterCache:
             self.close()
         except Exception:
             pass
+
+
+def verify(keys, key_begin, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10):
+    """Construction check (adl_bloom_verify): key i of host numpy `keys` belongs to the filter f with
+    key_begin[f] <= i < key_begin[f+1] and is probed against bitmaps[bitmap_off[f]:bitmap_off[f+1]].
+    Returns (keys the probe answers 0 for, index of the first one or None)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    kb = np.ascontiguousarray(key_begin, dtype=np.uint64)
+    bo = np.ascontiguousarray(bitmap_off, dtype=np.uint64)
+    bm = np.ascontiguousarray(bitmaps, dtype=np.uint8)
+    if len(bo) != len(kb):
+        raise ValueError("key_begin and bitmap_off need one entry per filter and one more")
+    if offsets is None:
+        n, stride, po = keys.shape[0], keys.shape[1], None
+    else:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n, stride, po = len(offsets) - 1, 0, offsets.ctypes.data
+    missing, first = ctypes.c_uint64(), ctypes.c_uint64()
+    kp = keys.ctypes.data if keys.size else np.zeros(16, np.uint8).ctypes.data
+    bp = bm.ctypes.data if bm.size else np.zeros(16, np.uint8).ctypes.data
+    _check(lib().adl_bloom_verify(kp, po, n, stride, kb.ctypes.data, len(kb) - 1, bp, bo.ctypes.data, bits_per_key,
+                                  ctypes.byref(missing), ctypes.byref(first), None), "adl_bloom_verify")
+    return missing.value, (None if missing.value == 0 else first.value)
 
 
 # ------------------------------------------------------------------ synthetic inputs

@@ -293,6 +293,17 @@ inline uint64_t bitmap_bytes(uint64_t n, int32_t bpk) {
 
 inline uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
+// Host memory the device can DMA directly (hipHostMalloc'd / registered).
+inline bool is_pinned(const void *p) {
+  if (!p) return false;
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();  // pageable memory: clear the sticky error
+    return false;
+  }
+  return attr.type == hipMemoryTypeHost;
+}
+
 // Per-thread staging for the synchronous host-pointer entry points: a pinned
 // host buffer (so every copy is a stream-ordered DMA; pageable hipMemcpyAsync
 // is not used anywhere) and a device buffer, both grown on demand and reused.
@@ -467,10 +478,18 @@ __attribute__((visibility("hidden"))) int adl_probe_fanout_device_ev(
     const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end, const uint8_t *d_k, uint8_t *d_out,
     hipStream_t st, hipEvent_t done);
 
+// Library-internal (filter_block_device.hip): adl_bloom_filter_block_build_device
+// with the segmented build's flags; in_place builds a one-filter block
+// straight into d_block (no staging, no pack, no trailer on the device).
+__attribute__((visibility("hidden"))) int adl_filter_block_build_into(
+    const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_stride, const uint64_t *key_begin,
+    uint32_t num_filters, int32_t bits_per_key, uint8_t *d_block, uint64_t block_bytes, uint32_t flags, bool in_place,
+    void *d_workspace, uint64_t workspace_bytes, hipStream_t st);
+
 // adl_bloom_test_fault's armed sites (-1: off).  take() disarms and returns the
 // argument, so an armed fault fires once.
 struct TestFaults {
-  std::atomic<int64_t> site[3] = {-1, -1, -1};
+  std::atomic<int64_t> site[4] = {-1, -1, -1, -1};
   int64_t take(int s) {
     if (site[s].load(std::memory_order_relaxed) < 0) return -1;
     return site[s].exchange(-1);

@@ -27,15 +27,7 @@ namespace {
 // keys per group, soft cap (at least one filter); ADL_BLOOM_PIPE_MB overrides
 constexpr uint64_t kGroupKeyBytes = 128ull << 20;  // measured: 32 MB 166 ms, 128 MB 76 ms, 512 MB 114 ms
 
-bool is_pinned(const void *p) {
-  if (!p) return false;
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();  // pageable memory: clear the sticky error
-    return false;
-  }
-  return attr.type == hipMemoryTypeHost;
-}
+using adl_host::is_pinned;
 
 // Per-thread buffers, grown on demand and reused (the C-ABI stays re-entrant).
 struct Pipe {

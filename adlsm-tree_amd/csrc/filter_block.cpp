@@ -247,7 +247,84 @@ RC FilterBlockWriter::Final(string &result) {
   return OK;
 }
 
+/* The same block through the write-through path: built in the cache's arena,
+ * held by `t` until the table's oid is known.  The keys stay in keys_ until
+ * the cache path has succeeded or failed for good, so a fallback builds from
+ * them as if nothing had happened. */
+RC FilterBlockWriter::Final(string &result, FilterCache &cache, FilterCacheTicket &t, bool verify) {
+  t = FilterCacheTicket();
+  auto *bloom = dynamic_cast<BloomFilter *>(method_.get());
+  if (!bloom || cache.status() != OK) return Final(result);
+  if (keys_.size() > bounds_.back()) Keys2Block();
+  const bool skip = dups_ * kSkipDuplicatesDen >= keys_.size() * kSkipDuplicatesNum && dups_ > 0;
+  const uint32_t flags = (skip ? ADL_BLOOM_SKIP_ADJACENT_DUPLICATES : 0u) | (verify ? ADL_BLOOM_CACHE_VERIFY : 0u);
+  const RC rc = cache.Build(keys_, bounds_, bloom->bits_per_key(), flags, buffer_, t);
+  if (rc != OK && rc != FILTER_BLOCK_ERROR) return Final(result);  // no room, too large, ...: the ordinary build
+  keys_.Clear();
+  bounds_.assign(1, 0);
+  dups_ = 0;
+  if (rc != OK) {
+    buffer_.clear();
+    return rc;
+  }
+  result = std::move(buffer_);
+  buffer_.clear();
+  return OK;
+}
+
 // ------------------------------------------------------------- FilterCache
+
+void FilterCacheTicket::Reset() {
+  if (t_) adl_bloom_filter_cache_abandon(cache_, t_);
+  t_ = nullptr;
+}
+
+RC FilterCache::Build(const KeyArena &keys, const vector<uint64_t> &key_begin, int bits_per_key, uint32_t flags,
+                      string &block, Ticket &t) {
+  t = Ticket();
+  if (!h_) return status_;
+  if (key_begin.empty() || key_begin.back() > keys.size()) return OUT_OF_RANGE;
+  const uint32_t nf = (uint32_t)(key_begin.size() - 1);
+  const uint64_t bytes = adl_bloom_filter_block_bytes(key_begin.data(), nf, bits_per_key);
+  if (bytes == 0) return OUT_OF_RANGE;
+  block.resize(bytes);
+  adl_bloom_cache_ticket *raw = nullptr;
+  const int st = adl_bloom_filter_cache_build(h_, reinterpret_cast<const uint8_t *>(keys.bytes().data()),
+                                              keys.offsets().data(), 0, key_begin.data(), nf, bits_per_key, flags,
+                                              reinterpret_cast<uint8_t *>(&block[0]), bytes, &raw, nullptr);
+  if (st != ADL_OK) {
+    block.clear();
+    return FromStatus(st);
+  }
+  t.cache_ = h_;
+  t.t_ = raw;
+  return OK;
+}
+
+RC FilterCache::Publish(Ticket &t, string_view oid) {
+  if (!t.t_ || t.cache_ != h_) return OUT_OF_RANGE;
+  adl_bloom_cache_ticket *raw = t.t_;
+  t.t_ = nullptr;  // consumed whatever the status
+  return FromStatus(adl_bloom_filter_cache_publish(h_, raw, oid.data(), oid.size()));
+}
+
+RC FilterCache::Abandon(Ticket &t) {
+  if (!t.t_ || t.cache_ != h_) return OUT_OF_RANGE;
+  t.Reset();
+  return OK;
+}
+
+uint64_t FilterCache::bytes_used() {
+  uint64_t b = 0;
+  if (h_) adl_bloom_filter_cache_stats(h_, nullptr, &b);
+  return b;
+}
+
+uint32_t FilterCache::tables() {
+  uint32_t n = 0;
+  if (h_) adl_bloom_filter_cache_stats(h_, &n, nullptr);
+  return n;
+}
 
 FilterCache::FilterCache(uint64_t capacity_bytes, uint32_t max_tables, int bits_per_key)
     : bits_per_key_(bits_per_key) {

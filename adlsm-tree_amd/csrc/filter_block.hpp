@@ -29,6 +29,7 @@
 
 struct adl_bloom_filter_set;
 struct adl_bloom_filter_cache;
+struct adl_bloom_cache_ticket;
 
 namespace adl {
 
@@ -122,6 +123,37 @@ class BloomFilter : public FilterAlgorithm {
   int k_;
 };
 
+class FilterCache;
+
+/* A filter block built into a FilterCache's arena and not yet published
+ * (adl_bloom_cache_ticket): FilterCache::Build makes it, Publish or Abandon
+ * consume it.  Move-only; a ticket destroyed while it still holds a range
+ * abandons it, so its cache must outlive it. */
+class FilterCacheTicket {
+ public:
+  FilterCacheTicket() = default;
+  ~FilterCacheTicket() { Reset(); }
+  FilterCacheTicket(FilterCacheTicket &&o) noexcept : cache_(o.cache_), t_(o.t_) { o.t_ = nullptr; }
+  FilterCacheTicket &operator=(FilterCacheTicket &&o) noexcept {
+    if (this != &o) {
+      Reset();
+      cache_ = o.cache_;
+      t_ = o.t_;
+      o.t_ = nullptr;
+    }
+    return *this;
+  }
+  FilterCacheTicket(const FilterCacheTicket &) = delete;
+  FilterCacheTicket &operator=(const FilterCacheTicket &) = delete;
+  explicit operator bool() const { return t_ != nullptr; }
+
+ private:
+  friend class FilterCache;
+  void Reset(); /* abandons */
+  adl_bloom_filter_cache *cache_ = nullptr;
+  adl_bloom_cache_ticket *t_ = nullptr;
+};
+
 /* src/filter_block.hpp:36-52 */
 class FilterBlockWriter {
  public:
@@ -130,6 +162,14 @@ class FilterBlockWriter {
   /* Update for a packed run (KeyArena::AddTrimmed): n keys, one reservation */
   RC UpdateBatch(const char *base, const uint64_t *off, size_t n, size_t trim);
   RC Final(string &result);
+  /* Final through the write-through path when the algorithm is the
+   * BloomFilter: the block (the same bytes) is built straight into `cache`'s
+   * arena and `t` holds it until FilterCache::Publish names its table; verify
+   * re-probes every key first (FILTER_BLOCK_ERROR when one is missing).  A
+   * cache-path failure that is not a filter error (no room in the arena, a
+   * block larger than it) and any other FilterAlgorithm fall back to
+   * Final(result) and leave `t` empty. */
+  RC Final(string &result, FilterCache &cache, FilterCacheTicket &t, bool verify);
   RC Keys2Block();
   /* keys added since the last Final that equal the previous key of their filter */
   uint64_t adjacent_duplicates() const { return dups_; }
@@ -162,6 +202,21 @@ class FilterCache {
   RC Put(string_view oid, string_view filter_block);
   bool Contains(string_view oid);
   bool Remove(string_view oid);
+  /* Write-through (adl_bloom_filter_cache_build): the filter block of `keys`
+   * (filter f = keys [key_begin[f], key_begin[f+1])) built straight into a
+   * reserved range of the arena.  `block` receives the reference's block for
+   * the file; `t` holds the range until Publish makes it the resident block
+   * of table `oid` (no re-upload) or Abandon gives it back.  flags:
+   * ADL_BLOOM_SKIP_ADJACENT_DUPLICATES, ADL_BLOOM_CACHE_VERIFY.  A build never
+   * waits for room held by unpublished tickets (DEVICE_ERROR instead). */
+  using Ticket = FilterCacheTicket;
+  RC Build(const KeyArena &keys, const vector<uint64_t> &key_begin, int bits_per_key, uint32_t flags, string &block,
+           Ticket &t);
+  RC Publish(Ticket &t, string_view oid);
+  RC Abandon(Ticket &t);
+  /* arena bytes in use (blocks, tickets' ranges) and cached tables */
+  uint64_t bytes_used();
+  uint32_t tables();
   /* One launch for the batch: out[i] = filter `filter` of table
    * oids[table[i]] may contain keys[i] (a table that is not cached answers 1,
    * "may be present"; *uncached counts those queries). */

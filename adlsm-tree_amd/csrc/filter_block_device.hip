@@ -172,20 +172,45 @@ int adl_bloom_filter_block_build_device(const uint8_t *d_keys, const uint64_t *d
                                         const uint64_t *key_begin, uint32_t num_filters, int32_t bits_per_key,
                                         uint8_t *d_block, uint64_t block_bytes, void *d_workspace,
                                         uint64_t workspace_bytes, void *stream) {
+  return adl_host::adl_filter_block_build_into(d_keys, d_offsets, key_stride, key_begin, num_filters, bits_per_key,
+                                               d_block, block_bytes, 0u, false, d_workspace, workspace_bytes,
+                                               (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// adl_bloom_filter_block_build_device with the segmented build's flags.
+// in_place (the filter cache's write-through build, cache_build.hip): a
+// one-filter block -- every SSTable's (src/sstable.cpp:21) -- is built straight
+// into d_block, whose only bitmap starts at offset 0 and so is 16-byte aligned
+// as the build kernels need: no staging copy, no pack launch, and no trailer
+// on the device (the caller frames it on the host).  The build writes the
+// bitmap's adl_bloom_bitmap_alloc_bytes there, pad bytes included: d_block
+// must have room for them.
+int adl_host::adl_filter_block_build_into(const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_stride,
+                                          const uint64_t *key_begin, uint32_t num_filters, int32_t bits_per_key,
+                                          uint8_t *d_block, uint64_t block_bytes, uint32_t flags, bool in_place,
+                                          void *d_workspace, uint64_t workspace_bytes, hipStream_t st) {
   try {
+    void *stream = st;
     Layout L;
     if (int rc = layout(key_begin, num_filters, bits_per_key, L)) return rc;
     if (!d_block || reinterpret_cast<uintptr_t>(d_block) % 16 || block_bytes < L.block_bytes)
       return ADL_ERR_INVALID_ARG;
     const uint64_t need = L.staging_bytes + 256 + build_ws(key_begin, num_filters, bits_per_key);
     if (!d_workspace || workspace_bytes < need) return ADL_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
+    if (in_place && num_filters == 1) {
+      if (block_bytes < adl_host::round_up(L.bytes[0], 16)) return ADL_ERR_INVALID_ARG;
+      return adl_bloom_build_segmented_device_ex(d_keys, d_offsets, key_stride, key_begin, 1, bits_per_key, d_block,
+                                                 L.dst.data(), flags, d_workspace, workspace_bytes, stream);
+    }
     uint8_t *staging = reinterpret_cast<uint8_t *>(adl_host::round_up(reinterpret_cast<uintptr_t>(d_workspace), 256));
     uint8_t *bws = staging + L.staging_bytes;
     const uint64_t bws_bytes = workspace_bytes - (uint64_t)(bws - reinterpret_cast<uint8_t *>(d_workspace));
     if (num_filters) {
-      const int rc = adl_bloom_build_segmented_device(d_keys, d_offsets, key_stride, key_begin, num_filters,
-                                                      bits_per_key, staging, L.src.data(), bws, bws_bytes, stream);
+      const int rc = adl_bloom_build_segmented_device_ex(d_keys, d_offsets, key_stride, key_begin, num_filters,
+                                                         bits_per_key, staging, L.src.data(), flags, bws, bws_bytes,
+                                                         stream);
       if (rc) return rc;
     }
     const uint32_t cus = adl_host::device_cus();
@@ -220,5 +245,3 @@ int adl_bloom_filter_block_build_device(const uint8_t *d_keys, const uint64_t *d
     return ADL_ERR_DEVICE;
   }
 }
-
-}  // extern "C"

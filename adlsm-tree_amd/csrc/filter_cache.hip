@@ -20,6 +20,10 @@
 //    cached answers 1 ("may be present": the caller reads the table), one
 //    bound for a filter the block does not have answers 0, as
 //    FilterBlockReader::IsKeyExists does (src/filter_block.cpp:174).
+//  * build / publish (cache_build.hip): a table's filter block built by the
+//    build kernels straight into a reserved range -- no upload at all -- and
+//    published under the oid once the file is written; the bookkeeping both
+//    files share is filter_cache_impl.hpp.
 //  * Concurrency: one mutex per cache guards the index, the LRU list and the
 //    arena's free list, and is held only for that bookkeeping -- never across
 //    a copy or a kernel.  A probe pins the entries it resolved (a count per
@@ -48,11 +52,12 @@
 
 #include "bloom_common.hpp"
 #include "filter_block_format.hpp"
+#include "filter_cache_impl.hpp"
 #include "probe_server.hpp"
 
 namespace {
 
-constexpr uint64_t kAlign = 256;
+using adl_cache::kAlign;
 constexpr uint64_t kOnesBytes = 16;  // an all-ones 16-byte filter: every probe hits
 constexpr int64_t kServerBackoffNs = 1000000000;  // launched probes for 1 s after a starved server request
 
@@ -90,88 +95,6 @@ struct DoneEvent {
 thread_local DoneEvent t_done;
 
 }  // namespace
-
-struct adl_bloom_filter_cache {
-  enum State : uint8_t { kLive, kLoading, kDead };
-  struct Entry {
-    std::string oid;
-    uint64_t base = 0, size = 0;  // arena range [base, base + size)
-    std::vector<uint64_t> off;    // block-relative filter offsets (F+1)
-    uint8_t k = 1;                // probes per key: from the block's own bits_per_key
-    uint32_t pins = 0;            // probes (or the uploading put) using the range
-    State state = kLive;
-  };
-  using Iter = std::list<Entry>::iterator;
-  std::mutex mu;
-  std::condition_variable freed;  // a dead or loading entry gave back its range
-  uint8_t *arena = nullptr;       // [ones][blocks...]
-  uint64_t capacity = 0, used = 0;
-  uint32_t max_tables = 0;
-  std::list<Entry> lru;      // live entries, front = most recently used
-  std::list<Entry> limbo;    // loading (pinned by their put) and dead (pinned by probes)
-  std::unordered_map<std::string, Iter> index;  // live entries only
-  std::map<uint64_t, uint64_t> free_;           // offset -> size, coalesced
-  // the resident probe server of this cache's small batches (created on the
-  // first one; srv_tried: do not retry a failed creation)
-  adl_srv::Server *srv = nullptr;
-  bool srv_tried = false;
-  // after a kBusy (the server's wave found no room on the GPU for
-  // adl_srv::kTimeout), small batches go straight to a launch until this
-  // steady-clock time (ns), instead of each waiting out the timeout again
-  std::atomic<int64_t> srv_backoff_until{0};
-  // published puts so far (the server invalidates its caches before it reads
-  // bits of a range that may have been written since it last did)
-  std::atomic<uint64_t> epoch{1};
-
-  bool alloc(uint64_t size, uint64_t &at) {
-    for (auto it = free_.begin(); it != free_.end(); ++it) {
-      if (it->second < size) continue;
-      at = it->first;
-      const uint64_t rest = it->second - size;
-      free_.erase(it);
-      if (rest) free_[at + size] = rest;
-      used += size;
-      return true;
-    }
-    return false;
-  }
-  void release(uint64_t at, uint64_t size) {
-    used -= size;
-    auto it = free_.emplace(at, size).first;
-    auto nx = std::next(it);
-    if (nx != free_.end() && it->first + it->second == nx->first) {
-      it->second += nx->second;
-      free_.erase(nx);
-    }
-    if (it != free_.begin()) {
-      auto pv = std::prev(it);
-      if (pv->first + pv->second == it->first) {
-        pv->second += it->second;
-        free_.erase(it);
-      }
-    }
-  }
-  // Take a live entry out of the index: its range is freed now, or -- while
-  // probes hold it -- by the last of them (unpin).
-  void retire(Iter it) {
-    index.erase(it->oid);
-    if (it->pins == 0) {
-      release(it->base, it->size);
-      lru.erase(it);
-      freed.notify_all();
-    } else {
-      it->state = kDead;
-      limbo.splice(limbo.end(), lru, it);
-    }
-  }
-  void unpin(Iter it) {
-    if (--it->pins == 0 && it->state == kDead) {
-      release(it->base, it->size);
-      limbo.erase(it);
-      freed.notify_all();
-    }
-  }
-};
 
 namespace {
 
@@ -289,6 +212,7 @@ int adl_bloom_filter_cache_create(uint64_t capacity_bytes, uint32_t max_tables, 
 int adl_bloom_filter_cache_destroy(adl_bloom_filter_cache *c) {
   if (!c) return ADL_OK;
   adl_srv::destroy(c->srv);  // stops its kernel before the arena goes
+  if (c->verify_slots) (void)hipHostFree(c->verify_slots);
   (void)hipFree(c->arena);
   delete c;
   return ADL_OK;
@@ -346,14 +270,7 @@ int adl_bloom_filter_cache_put(adl_bloom_filter_cache *c, const char *oid, uint6
       c->unpin(mine);
       return ADL_ERR_DEVICE;
     }
-    if (auto it = c->index.find(key); it != c->index.end()) c->retire(it->second);  // the block this one replaces
-    mine->pins = 0;
-    mine->state = adl_bloom_filter_cache::kLive;
-    c->lru.splice(c->lru.begin(), c->limbo, mine);
-    c->index[key] = c->lru.begin();
-    c->epoch.fetch_add(1, std::memory_order_release);  // (under the lock: before any probe can resolve it)
-    while (c->lru.size() > c->max_tables) c->retire(std::prev(c->lru.end()));
-    c->freed.notify_all();  // a put waiting for room may evict this entry now
+    c->publish(mine, key);
     return ADL_OK;
   } catch (...) {
     return ADL_ERR_OUT_OF_MEMORY;

@@ -285,7 +285,7 @@ RC SSTableWriter::Final(unsigned char sha256_digit[32]) {
   RC rc;
   if (!data_block_.Empty() && (rc = FlushDataBlock())) return rc;
   const auto f0 = std::chrono::steady_clock::now();
-  rc = filter_block_.Final(filter_out_);  // the reference drops this RC
+  rc = BuildFilter(ticket_);  // the reference drops this RC
   filter_seconds_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - f0).count();
   if (rc) return rc;
   return WriteTail(sha256_digit);
@@ -299,23 +299,48 @@ RC SSTableWriter::BeginFinal() {
   if (adl_bloom_get_device(&dev) != ADL_OK) return DEVICE_ERROR;
   // the worker owns filter_block_ and filter_out_ until EndFinal's get()
   filter_job_ = FilterWorker::ForThisThread().Post([this, dev]() -> FilterOutcome {
-    if (adl_bloom_set_device(dev) != ADL_OK) return {DEVICE_ERROR, 0.0};
+    if (adl_bloom_set_device(dev) != ADL_OK) return {DEVICE_ERROR, 0.0, {}};
     const auto f0 = std::chrono::steady_clock::now();
-    const RC r = filter_block_.Final(filter_out_);
-    return {r, std::chrono::duration<double>(std::chrono::steady_clock::now() - f0).count()};
+    FilterOutcome out{OK, 0.0, {}};  // the ticket travels back with the outcome
+    out.rc = BuildFilter(out.ticket);
+    out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - f0).count();
+    return out;
   });
   return OK;
 }
 
 RC SSTableWriter::EndFinal(unsigned char sha256_digit[32]) {
   if (!filter_job_.valid()) return BAD_RECORD;
-  const FilterOutcome out = filter_job_.get();
+  FilterOutcome out = filter_job_.get();
   filter_seconds_ = out.seconds;
+  ticket_ = std::move(out.ticket);
   if (out.rc) return out.rc;
   return WriteTail(sha256_digit);
 }
 
+/* The filter block into filter_out_: through the filter cache when one is
+ * set (t then holds the block's range in its arena), else the ordinary build. */
+RC SSTableWriter::BuildFilter(FilterCacheTicket &t) {
+  if (cache_) return filter_block_.Final(filter_out_, *cache_, t, verify_);
+  return filter_block_.Final(filter_out_);
+}
+
+/* The rest of the file, then the built filter block's fate: resident under
+ * the oid once the file stands (its SHA-256 is the oid, so only now is it
+ * known), given back when the write failed.  A publish that fails leaves a
+ * good file whose table is merely not cached: readers put it as before. */
 RC SSTableWriter::WriteTail(unsigned char sha256_digit[32]) {
+  const RC rc = WriteTailBlocks(sha256_digit);
+  if (ticket_) {
+    if (rc == OK)
+      (void)cache_->Publish(ticket_, Sha256Hex(sha256_digit));
+    else
+      (void)cache_->Abandon(ticket_);
+  }
+  return rc;
+}
+
+RC SSTableWriter::WriteTailBlocks(unsigned char sha256_digit[32]) {
   RC rc;
   buffer_ = std::move(filter_out_);
   if ((rc = Emit(buffer_))) return rc;

@@ -127,10 +127,12 @@ class PosixFileSink : public Sink {
   int fd_ = -1;
 };
 
-/* what a filter build hands back to EndFinal */
+/* what a filter build hands back to EndFinal (ticket: the block's range in the
+ * writer's filter cache, when it was built there) */
 struct FilterOutcome {
   RC rc;
   double seconds;
+  FilterCacheTicket ticket;
 };
 
 /* src/sstable.hpp:21-71 */
@@ -161,6 +163,19 @@ class SSTableWriter {
    * are the same as Final's.  Final itself builds on the calling thread. */
   RC BeginFinal();
   RC EndFinal(unsigned char sha256_digit[32]);
+  /* Write-through: Final and BeginFinal / EndFinal build the filter block
+   * straight into `cache`'s arena (FilterBlockWriter::Final's cache overload)
+   * and, once sink->Finish(oid) has succeeded, publish it under the hex oid:
+   * the table this writer wrote is resident with no Put and no re-upload.  The
+   * file bytes and the oid are the same with and without a cache.  A cache-path
+   * failure that is not a filter error falls back to the ordinary build; a
+   * failed file write gives the range back.  verify: every filter key is
+   * probed again before the block may go resident (FILTER_BLOCK_ERROR when one
+   * is missing).  `cache` must outlive the writer; nullptr switches it off. */
+  void SetFilterCache(FilterCache *cache, bool verify = false) {
+    cache_ = cache;
+    verify_ = verify;
+  }
   int GetFileSize() const { return offset_; }
   /* filter keys added so far that equal their predecessor (user keys of
    * consecutive versions); Final skips them on the device when frequent */
@@ -173,8 +188,13 @@ class SSTableWriter {
   RC FlushDataBlock();
   RC Emit(const string &block);
   RC WriteTail(unsigned char sha256_digit[32]);
+  RC WriteTailBlocks(unsigned char sha256_digit[32]);
+  RC BuildFilter(FilterCacheTicket &t);
 
   Sink *sink_;
+  FilterCache *cache_ = nullptr; /* SetFilterCache */
+  bool verify_ = false;
+  FilterCacheTicket ticket_;     /* the built block's range, between the build and WriteTail */
   int offset_ = 0;
   Sha256 sha256_;
   BlockWriter data_block_, index_block_, meta_data_block_;

@@ -342,6 +342,106 @@ int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *cache, const cha
                                         const uint32_t *h_pair_table, uint8_t *h_out, uint64_t *h_uncached,
                                         void *stream);
 
+/* ------------------------------------------- write-through builds into the cache */
+
+/* A table's filter block built straight into a reserved range of the cache
+ * arena (SSTableWriter::Final, src/sstable.cpp:58): the block comes back to
+ * the host for the file, and the range is published under the table's oid
+ * once that is known (the oid is the SHA-256 of the finished file).  No
+ * re-upload of the block, and no window in which a freshly written table
+ * answers "not cached".  A ticket stands for the built, unpublished range. */
+typedef struct adl_bloom_cache_ticket adl_bloom_cache_ticket;
+
+/* With ADL_BLOOM_SKIP_ADJACENT_DUPLICATES (1u) in one flags word: every build
+ * key is probed again against the bitmap it went into
+ * (adl_bloom_verify_device) before the block may go resident; a key that is
+ * missing fails the build with ADL_FILTER_BLOCK_ERROR. */
+#define ADL_BLOOM_CACHE_VERIFY 2u
+
+/* Build num_filters filters from HOST keys (filter f = keys [key_begin[f],
+ * key_begin[f+1]), HOST array of num_filters+1 entries) into a range of
+ * round_up(max(block bytes, bitmap bytes + 1), 256) arena bytes, reserved as
+ * adl_bloom_filter_cache_put reserves its range (least recently used blocks
+ * are evicted for it), and write the block -- exactly
+ * adl_bloom_filter_block_bytes bytes, byte-identical to
+ * adl_bloom_filter_block_build_device followed by a D2H -- to h_block
+ * (block_bytes smaller than that: ADL_ERR_INVALID_ARG).  Pinned key and block
+ * buffers are DMAed directly, pageable ones staged through the thread's
+ * pinned buffer.  A one-filter block is built in place (no staging, no pack
+ * launch); the trailer is framed on the host.  *ticket receives the handle
+ * for publish / abandon.  Unlike put, a build never waits for room that only
+ * unpublished tickets hold (a thread holding two tickets would wait for
+ * itself): it returns ADL_ERR_OUT_OF_MEMORY and leaves the cache as it was.
+ * With ADL_BLOOM_CACHE_VERIFY the result is read before the call returns: on
+ * a missing key the range is released, no ticket is made and the status is
+ * ADL_FILTER_BLOCK_ERROR.  Unknown flag bits: ADL_ERR_INVALID_ARG.
+ * Synchronous.
+ *
+ * A ticket nobody publishes or abandons holds its range like any block being
+ * uploaded: a put in need of that room waits for it.  Destroying a cache
+ * with tickets outstanding is the caller's error, as a running call is. */
+int adl_bloom_filter_cache_build(adl_bloom_filter_cache *cache, const uint8_t *h_keys,
+                                 const uint64_t *h_offsets, uint32_t key_stride, const uint64_t *key_begin,
+                                 uint32_t num_filters, int32_t bits_per_key, uint32_t flags, uint8_t *h_block,
+                                 uint64_t block_bytes, adl_bloom_cache_ticket **ticket, void *stream);
+
+/* Device bytes adl_bloom_filter_cache_build_device needs (>=
+ * adl_bloom_filter_block_workspace_bytes); 0 on invalid input or a block
+ * beyond the reference's int offsets. */
+uint64_t adl_bloom_filter_cache_build_workspace_bytes(const uint64_t *key_begin, uint32_t num_filters,
+                                                      int32_t bits_per_key);
+
+/* The same build from DEVICE keys: enqueues on `stream` and does not
+ * synchronise.  h_block may be NULL (no download); otherwise the bitmaps are
+ * copied into it on `stream` (pinned memory keeps that asynchronous) and the
+ * trailer is written by the host before the call returns, so the block is
+ * complete once the stream's work is.  d_workspace (256-byte aligned) must
+ * stay untouched until then.  adl_bloom_filter_cache_publish waits for the
+ * build itself (an event recorded on `stream`), and with
+ * ADL_BLOOM_CACHE_VERIFY reads the verify result there. */
+int adl_bloom_filter_cache_build_device(adl_bloom_filter_cache *cache, const uint8_t *d_keys,
+                                        const uint64_t *d_offsets, uint32_t key_stride,
+                                        const uint64_t *key_begin, uint32_t num_filters, int32_t bits_per_key,
+                                        uint32_t flags, void *d_workspace, uint64_t workspace_bytes,
+                                        uint8_t *h_block, uint64_t block_bytes, adl_bloom_cache_ticket **ticket,
+                                        void *stream);
+
+/* Make the built block the most recently used block of table `oid`,
+ * replacing one cached under that oid; max_tables is enforced as in put.
+ * Waits for the build's work first.  A device-variant build made with
+ * ADL_BLOOM_CACHE_VERIFY that has a missing key releases the range instead
+ * and returns ADL_FILTER_BLOCK_ERROR.  The ticket is consumed whatever the
+ * status (except ADL_ERR_INVALID_ARG for a NULL argument). */
+int adl_bloom_filter_cache_publish(adl_bloom_filter_cache *cache, adl_bloom_cache_ticket *ticket,
+                                   const char *oid, uint64_t oid_len);
+
+/* Give the range back (waits for the build's work first).  Consumes the ticket. */
+int adl_bloom_filter_cache_abandon(adl_bloom_filter_cache *cache, adl_bloom_cache_ticket *ticket);
+
+/* Construction check: probe every build key against the filter it belongs
+ * to.  Key i (of n) belongs to filter f with d_key_begin[f] <= i <
+ * d_key_begin[f+1] (DEVICE array, num_filters+1 entries, non-decreasing);
+ * filter f = d_bitmaps[d_begin[f] .. d_end[f]) as in
+ * adl_bloom_probe_ranges_device (d_end == NULL: d_begin has num_filters+1
+ * entries).  d_result[0] = the number of keys the probe answers 0 for,
+ * d_result[1] = the index of the first of them, or ~0 when there is none: 0
+ * and ~0 after any correct build.  A key whose filter is empty or has 2^31
+ * bits or more counts as missing (the probe would answer 0); a key outside
+ * [d_key_begin[0], d_key_begin[num_filters]) was not built into any filter
+ * and is not checked.  d_result is initialised on `stream` before the launch. */
+int adl_bloom_verify_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n, uint32_t key_stride,
+                            const uint64_t *d_key_begin, uint32_t num_filters, const uint8_t *d_bitmaps,
+                            const uint64_t *d_begin, const uint64_t *d_end, int32_t bits_per_key,
+                            uint64_t *d_result, void *stream);
+
+/* Host-pointer convenience: filter f = h_bitmaps[h_bitmap_off[f] ..
+ * h_bitmap_off[f+1]) (HOST arrays; key_begin and h_bitmap_off have
+ * num_filters+1 entries).  *first_missing = ~0 when *missing = 0.  Synchronous. */
+int adl_bloom_verify(const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t n, uint32_t key_stride,
+                     const uint64_t *key_begin, uint32_t num_filters, const uint8_t *h_bitmaps,
+                     const uint64_t *h_bitmap_off, int32_t bits_per_key, uint64_t *missing,
+                     uint64_t *first_missing, void *stream);
+
 /* ---------------------------------------------------------------- hash */
 
 /* The reference's murmur3 variant (src/murmur3_hash.cpp:11-65) on the GPU for a
@@ -388,9 +488,15 @@ int adl_bloom_build_positions(const uint64_t *key_counts, uint32_t num_filters, 
  * call fails in its group g's build, with earlier groups' copies in flight.
  * ADL_TEST_FAULT_CACHE_COMPLETION, arg >= 0: the next filter-cache probe that
  * waits for its answers in the mapped buffer sees its kernel's completion
- * report a device error after all answers have arrived.  arg < 0 disarms. */
+ * report a device error after all answers have arrived.
+ * ADL_TEST_FAULT_CACHE_BUILD_CORRUPT, arg >= 0: the next write-through cache
+ * build clears the first non-zero byte of filter 0's bitmap in its arena
+ * range, after the build and before verification (corrupted data, nothing
+ * faults): the only way to see ADL_BLOOM_CACHE_VERIFY reject a build.
+ * arg < 0 disarms. */
 #define ADL_TEST_FAULT_PIPELINE_GROUP 1
 #define ADL_TEST_FAULT_CACHE_COMPLETION 2
+#define ADL_TEST_FAULT_CACHE_BUILD_CORRUPT 3
 int adl_bloom_test_fault(int site, int64_t arg);
 
 /* The tuning and test switches (ADL_BLOOM_* environment variables, DESIGN.md
