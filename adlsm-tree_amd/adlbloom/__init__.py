@@ -188,6 +188,28 @@ def _stream(stream=None):
     return ctypes.c_void_p(stream.cuda_stream)
 
 
+def _host_stream(stream=None):
+    """`stream` of a host-pointer entry point: None is NULL there, the calling
+    thread's own non-blocking stream (include/adl_bloom.h)."""
+    return None if stream is None else ctypes.c_void_p(stream.cuda_stream)
+
+
+def _on(stream):
+    """Context in which a wrapper allocates what its call uses on `stream`:
+    torch's caching allocator hands memory out per stream -- a block is reused
+    only in the order of the stream it was allocated for -- so outputs and
+    workspaces are allocated with `stream` current.  Their first use then
+    follows whatever used the block before, and a workspace dropped when the
+    wrapper returns is reused only behind the call's work, with nothing to
+    synchronise.  None: the current stream, as ever."""
+    return _torch().cuda.stream(stream)
+
+
+def _sync(stream=None):
+    """Wait for the stream a wrapper was given (None: the current stream)."""
+    (_torch().cuda.current_stream() if stream is None else stream).synchronize()
+
+
 def _dptr(t) -> int | None:
     if t is None:
         return None
@@ -221,7 +243,9 @@ class Builder:
         self.ws = empty_device(self.ws_bytes, device)
 
     def positions(self, stream=None) -> int:
-        """Positions (bit-sets after repeated pairs were skipped) the last build wrote."""
+        """Positions (bit-sets after repeated pairs were skipped) this builder's last build wrote,
+        whatever else the thread has built since.  Pass the build's `stream`: the readback is then
+        ordered after the build and needs no synchronise in between."""
         cnt = np.array([self.n], dtype=np.uint64)
         v = ctypes.c_uint64()
         _check(lib().adl_bloom_build_positions(cnt.ctypes.data, 1, self.bpk, _dptr(self.ws), ctypes.byref(v),
@@ -263,7 +287,9 @@ class SegmentedBuilder:
         return self.out
 
     def positions(self, stream=None) -> int:
-        """Positions (bit-sets after repeated pairs were skipped) the last build wrote."""
+        """Positions (bit-sets after repeated pairs were skipped) this builder's last build wrote,
+        whatever else the thread has built since.  Pass the build's `stream`: the readback is then
+        ordered after the build and needs no synchronise in between."""
         counts = np.ascontiguousarray(self.kb[1:] - self.kb[:-1], dtype=np.uint64)
         v = ctypes.c_uint64()
         _check(lib().adl_bloom_build_positions(counts.ctypes.data, len(counts), self.bpk, _dptr(self.ws),
@@ -278,7 +304,9 @@ class SegmentedBuilder:
 def build(keys, offsets=None, bits_per_key: int = 10, stream=None):
     """Keys2Block on the GPU: returns the (n*bpk+7)-byte bitmap as a uint8 device tensor."""
     pk, po, n, stride = _keyset(keys, offsets)
-    return Builder(n, bits_per_key, keys.device).build(keys, offsets, stream)
+    with _on(stream):  # (the workspace is dropped here, with the build perhaps still running)
+        b = Builder(n, bits_per_key, keys.device)
+    return b.build(keys, offsets, stream)
 
 
 SKIP_ADJACENT_DUPLICATES = 1
@@ -297,16 +325,18 @@ def build_segmented(keys, key_begin, offsets=None, bits_per_key: int = 10, strea
     boff = np.zeros(F, dtype=np.uint64)
     if F > 1:
         boff[1:] = np.cumsum(alloc[:-1])
-    out = empty_device(int(alloc.sum()), keys.device)
+    with _on(stream):
+        out = empty_device(int(alloc.sum()), keys.device)
     ws_bytes = workspace_bytes(counts, bits_per_key)
-    ws = empty_device(ws_bytes, keys.device)
+    with _on(stream):
+        ws = empty_device(ws_bytes, keys.device)
     pk = _dptr(keys)
     po = _dptr(offsets)
     stride = 0 if offsets is not None else keys.shape[1]
     _check(lib().adl_bloom_build_segmented_device_ex(pk, po, stride, kb.ctypes.data, F, bits_per_key,
                                                      _dptr(out), boff.ctypes.data, flags, _dptr(ws), ws_bytes,
                                                      _stream(stream)), "adl_bloom_build_segmented_device_ex")
-    torch.cuda.current_stream().synchronize()  # ws/out lifetimes end with this call's tensors
+    _sync(stream)  # ws/out lifetimes end with this call's tensors
     return out, boff, sizes
 
 
@@ -327,13 +357,14 @@ def build_filter_block(keys, key_begin, offsets=None, bits_per_key: int = 10, st
         raise AdlBloomError(-2, "filter block size")
     ws_bytes = L.adl_bloom_filter_block_workspace_bytes(kb.ctypes.data, F, bits_per_key)
     dev = keys.device if keys is not None else "cuda"
-    block = empty_device(nbytes, dev)
-    ws = empty_device(ws_bytes, dev)
+    with _on(stream):
+        block = empty_device(nbytes, dev)
+        ws = empty_device(ws_bytes, dev)
     stride = 0 if offsets is not None else (int(keys.shape[1]) if keys is not None else 16)
     _check(L.adl_bloom_filter_block_build_device(_dptr(keys), _dptr(offsets), stride, kb.ctypes.data, F,
                                                  bits_per_key, _dptr(block), nbytes, _dptr(ws), ws_bytes,
                                                  _stream(stream)), "adl_bloom_filter_block_build_device")
-    _torch().cuda.current_stream().synchronize()  # ws lifetime ends with this call
+    _sync(stream)  # ws lifetime ends with this call
     return block[:nbytes]
 
 
@@ -368,7 +399,8 @@ def probe(keys, bitmap, nbytes: int | None = None, offsets=None, bits_per_key: i
     """IsKeyExists on the GPU for a batch: uint8 device tensor of 0/1."""
     pk, po, n, stride = _keyset(keys, offsets)
     nbytes = bitmap.numel() if nbytes is None else nbytes
-    out = _torch().empty(max(n, 1), dtype=_torch().uint8, device=keys.device)
+    with _on(stream):
+        out = _torch().empty(max(n, 1), dtype=_torch().uint8, device=keys.device)
     _check(lib().adl_bloom_probe_device(pk, po, n, stride, bits_per_key, _dptr(bitmap), nbytes,
                                         _dptr(out), _stream(stream)), "adl_bloom_probe_device")
     return out[:n]
@@ -377,7 +409,8 @@ def probe(keys, bitmap, nbytes: int | None = None, offsets=None, bits_per_key: i
 def probe_multi(keys, filter_id, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10, stream=None):
     """Key i against filter filter_id[i]; bitmap_off: device uint64 tensor (F+1)."""
     pk, po, n, stride = _keyset(keys, offsets)
-    out = _torch().empty(max(n, 1), dtype=_torch().uint8, device=keys.device)
+    with _on(stream):
+        out = _torch().empty(max(n, 1), dtype=_torch().uint8, device=keys.device)
     _check(lib().adl_bloom_probe_multi_device(pk, po, n, stride, _dptr(filter_id), bitmap_off.numel() - 1,
                                               _dptr(bitmaps), _dptr(bitmap_off), bits_per_key,
                                               _dptr(out), _stream(stream)), "adl_bloom_probe_multi_device")
@@ -391,7 +424,8 @@ def probe_fanout(keys, pair_begin, pair_filter, bitmaps, bitmap_off, offsets=Non
     pk, po, n, stride = _keyset(keys, offsets)
     assert pair_begin.numel() == n + 1, "pair_begin: one entry per key and one more"
     npairs = pair_filter.numel()
-    out = _torch().empty(max(npairs, 1), dtype=_torch().uint8, device=keys.device)
+    with _on(stream):
+        out = _torch().empty(max(npairs, 1), dtype=_torch().uint8, device=keys.device)
     _check(lib().adl_bloom_probe_fanout_device(pk, po, n, stride, _dptr(pair_begin), _dptr(pair_filter), npairs,
                                                bitmap_off.numel() - 1, _dptr(bitmaps), _dptr(bitmap_off), None,
                                                bits_per_key, _dptr(out), _stream(stream)),
@@ -409,9 +443,11 @@ def probe_batch(keys, filter_id, bitmaps, bitmap_off, offsets=None, bits_per_key
     F = bitmap_off.numel() - (0 if bitmap_end is not None else 1)
     L = lib()
     wsb = L.adl_bloom_probe_batch_workspace_bytes(n, F, bits_per_key, stride)
-    ws = empty_device(wsb, keys.device)
+    with _on(stream):
+        ws = empty_device(wsb, keys.device)
     if out is None:
-        out = _torch().empty(max(n, 1), dtype=_torch().uint8, device=keys.device)
+        with _on(stream):
+            out = _torch().empty(max(n, 1), dtype=_torch().uint8, device=keys.device)
     elif out.dtype != _torch().uint8 or out.numel() < n or not out.is_contiguous():
         raise ValueError("out must be a contiguous uint8 tensor of at least n elements")
     _check(L.adl_bloom_probe_batch_device(pk, po, n, stride, _dptr(filter_id), F, _dptr(bitmaps), _dptr(bitmap_off),
@@ -422,7 +458,8 @@ def probe_batch(keys, filter_id, bitmaps, bitmap_off, offsets=None, bits_per_key
 
 def murmur3_batch(keys, offsets=None, seed_a=SEED1, seed_b=SEED2, stream=None):
     pk, po, n, stride = _keyset(keys, offsets)
-    out = _torch().empty((max(n, 1), 2), dtype=_torch().int32, device=keys.device)
+    with _on(stream):
+        out = _torch().empty((max(n, 1), 2), dtype=_torch().int32, device=keys.device)
     _check(lib().adl_bloom_murmur3_device(pk, po, n, stride, seed_a, seed_b, _dptr(out), _stream(stream)),
            "adl_bloom_murmur3_device")
     return out[:n]
@@ -478,8 +515,10 @@ def profile_collect():
 
 # ------------------------------------------------------------------ host-pointer API
 def build_host(keys: np.ndarray, offsets: np.ndarray | None = None, bits_per_key: int = 10,
-               out: np.ndarray | None = None) -> np.ndarray:
+               out: np.ndarray | None = None, stream=None) -> np.ndarray:
     """adl_bloom_build: host keys in, host bitmap out (upload + build + download).
+    `stream` (here and in the other host-pointer wrappers): a torch stream to run
+    on, or None for the calling thread's own non-blocking stream.
     `out`: an optional uint8 host array (any alignment; pinned or pageable) of
     at least the bitmap's size to write it into."""
     keys = np.ascontiguousarray(keys, dtype=np.uint8)
@@ -496,12 +535,13 @@ def build_host(keys: np.ndarray, offsets: np.ndarray | None = None, bits_per_key
     elif out.dtype != np.uint8 or out.size < nb or not out.flags["C_CONTIGUOUS"]:
         raise ValueError("out must be a contiguous uint8 array of at least the bitmap's size")
     kp = keys.ctypes.data if keys.size else np.zeros(1, np.uint8).ctypes.data
-    _check(lib().adl_bloom_build(kp, po, n, stride, bits_per_key, out.ctypes.data, None), "adl_bloom_build")
+    _check(lib().adl_bloom_build(kp, po, n, stride, bits_per_key, out.ctypes.data, _host_stream(stream)),
+           "adl_bloom_build")
     return out[:nb]
 
 
 def probe_host(keys: np.ndarray, bitmap: np.ndarray, offsets: np.ndarray | None = None,
-               bits_per_key: int = 10) -> np.ndarray:
+               bits_per_key: int = 10, stream=None) -> np.ndarray:
     keys = np.ascontiguousarray(keys, dtype=np.uint8)
     bitmap = np.ascontiguousarray(bitmap, dtype=np.uint8)
     if offsets is None:
@@ -511,7 +551,7 @@ def probe_host(keys: np.ndarray, bitmap: np.ndarray, offsets: np.ndarray | None 
         n, stride, po = len(offsets) - 1, 0, offsets.ctypes.data
     out = np.empty(max(n, 1), dtype=np.uint8)
     _check(lib().adl_bloom_probe(keys.ctypes.data, po, n, stride, bits_per_key, bitmap.ctypes.data,
-                                 bitmap.size, out.ctypes.data, None), "adl_bloom_probe")
+                                 bitmap.size, out.ctypes.data, _host_stream(stream)), "adl_bloom_probe")
     return out[:n]
 
 
@@ -526,7 +566,7 @@ class FilterSet:
                                                  bits_per_key, ctypes.byref(self._h)),
                "adl_bloom_filter_set_create")
 
-    def probe(self, keys: np.ndarray, filter_id=None, filter: int = 0, offsets=None) -> np.ndarray:
+    def probe(self, keys: np.ndarray, filter_id=None, filter: int = 0, offsets=None, stream=None) -> np.ndarray:
         keys = np.ascontiguousarray(keys, dtype=np.uint8)
         if offsets is None:
             n, stride, po = keys.shape[0], keys.shape[1], None
@@ -537,7 +577,7 @@ class FilterSet:
         out = np.empty(max(n, 1), dtype=np.uint8)
         _check(lib().adl_bloom_filter_set_probe(self._h, keys.ctypes.data, po, n, stride,
                                                 None if fid is None else fid.ctypes.data, filter,
-                                                out.ctypes.data, None), "adl_bloom_filter_set_probe")
+                                                out.ctypes.data, _host_stream(stream)), "adl_bloom_filter_set_probe")
         return out[:n]
 
     def close(self):
@@ -580,7 +620,7 @@ class FilterCache:
         _check(lib().adl_bloom_filter_cache_stats(self._h, ctypes.byref(t), ctypes.byref(b)), "stats")
         return t.value, b.value
 
-    def probe(self, oids, table, keys: np.ndarray, offsets=None, filter: int = 0):
+    def probe(self, oids, table, keys: np.ndarray, offsets=None, filter: int = 0, stream=None):
         """Query i against filter `filter` of table oids[table[i]]; returns (0/1 array, uncached count)."""
         keys = np.ascontiguousarray(keys, dtype=np.uint8)
         if offsets is None:
@@ -595,11 +635,12 @@ class FilterCache:
         unc = ctypes.c_uint64()
         _check(lib().adl_bloom_filter_cache_probe(self._h, arr, lens.ctypes.data, len(oids), filter,
                                                   keys.ctypes.data, po, n, stride, tab.ctypes.data,
-                                                  out.ctypes.data, ctypes.byref(unc), None),
+                                                  out.ctypes.data, ctypes.byref(unc), _host_stream(stream)),
                "adl_bloom_filter_cache_probe")
         return out[:n], unc.value
 
-    def probe_fanout(self, oids, pair_begin, pair_table, keys: np.ndarray, offsets=None, filter: int = 0):
+    def probe_fanout(self, oids, pair_begin, pair_table, keys: np.ndarray, offsets=None, filter: int = 0,
+                     stream=None):
         """Key i against filter `filter` of every table oids[t], t in pair_table[pair_begin[i]:pair_begin[i+1]];
         returns (0/1 per pair in pair order, uncached pair count): probe() on the expanded pairs, each key
         uploaded and hashed once."""
@@ -622,7 +663,7 @@ class FilterCache:
         kp = keys.ctypes.data if keys.size else np.zeros(1, np.uint8).ctypes.data
         _check(lib().adl_bloom_filter_cache_probe_fanout(self._h, arr, lens.ctypes.data, len(oids), filter, kp, po,
                                                          n, stride, pb.ctypes.data, tab.ctypes.data, out.ctypes.data,
-                                                         ctypes.byref(unc), None),
+                                                         ctypes.byref(unc), _host_stream(stream)),
                "adl_bloom_filter_cache_probe_fanout")
         return out[:len(tab)], unc.value
 
@@ -638,7 +679,7 @@ class FilterCache:
         def block_bytes(self) -> bytes:
             return bytes(self.block[:self.nbytes].numpy().tobytes())
 
-    def build_status(self, keys, key_begin, offsets=None, bits_per_key: int = 10, flags: int = 0):
+    def build_status(self, keys, key_begin, offsets=None, bits_per_key: int = 10, flags: int = 0, stream=None):
         """adl_bloom_filter_cache_build on host numpy keys: (status, block bytes or None, ticket or None)."""
         keys = np.ascontiguousarray(keys, dtype=np.uint8)
         kb = np.ascontiguousarray(key_begin, dtype=np.uint64)
@@ -652,16 +693,17 @@ class FilterCache:
         kp = keys.ctypes.data if keys.size else np.zeros(16, np.uint8).ctypes.data
         h = ctypes.c_void_p()
         rc = lib().adl_bloom_filter_cache_build(self._h, kp, po, stride, kb.ctypes.data, len(kb) - 1, bits_per_key,
-                                                flags, block.ctypes.data, nbytes, ctypes.byref(h), None)
+                                                flags, block.ctypes.data, nbytes, ctypes.byref(h),
+                                                _host_stream(stream))
         if rc != ADL_OK:
             return rc, None, None
         return rc, block[:nbytes].tobytes(), FilterCache.Ticket(h)
 
-    def build(self, keys, key_begin, offsets=None, bits_per_key: int = 10, flags: int = 0):
+    def build(self, keys, key_begin, offsets=None, bits_per_key: int = 10, flags: int = 0, stream=None):
         """Build the filter block of keys (filter f = keys [key_begin[f], key_begin[f+1])) into a reserved
         range of the arena: returns (block: bytes, ticket).  The block is the reference's, for the file;
         publish(ticket, oid) makes it resident under the table's oid, abandon(ticket) gives the range back."""
-        rc, block, t = self.build_status(keys, key_begin, offsets, bits_per_key, flags)
+        rc, block, t = self.build_status(keys, key_begin, offsets, bits_per_key, flags, stream)
         _check(rc, "adl_bloom_filter_cache_build")
         return block, t
 
@@ -678,7 +720,8 @@ class FilterCache:
         wsb = L.adl_bloom_filter_cache_build_workspace_bytes(kb.ctypes.data, len(kb) - 1, bits_per_key)
         if nbytes == 0 or wsb == 0:
             raise AdlBloomError(-2, "filter block size")
-        ws = empty_device(wsb, keys.device if keys is not None else "cuda")
+        with _on(stream):
+            ws = empty_device(wsb, keys.device if keys is not None else "cuda")
         if isinstance(h_block, str):
             h_block = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
         stride = 0 if offsets is not None else (int(keys.shape[1]) if keys is not None else 16)
@@ -723,7 +766,7 @@ class FilterCache:
             pass
 
 
-def verify(keys, key_begin, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10):
+def verify(keys, key_begin, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10, stream=None):
     """Construction check (adl_bloom_verify): key i of host numpy `keys` belongs to the filter f with
     key_begin[f] <= i < key_begin[f+1] and is probed against bitmaps[bitmap_off[f]:bitmap_off[f+1]].
     Returns (keys the probe answers 0 for, index of the first one or None)."""
@@ -742,14 +785,16 @@ def verify(keys, key_begin, bitmaps, bitmap_off, offsets=None, bits_per_key: int
     kp = keys.ctypes.data if keys.size else np.zeros(16, np.uint8).ctypes.data
     bp = bm.ctypes.data if bm.size else np.zeros(16, np.uint8).ctypes.data
     _check(lib().adl_bloom_verify(kp, po, n, stride, kb.ctypes.data, len(kb) - 1, bp, bo.ctypes.data, bits_per_key,
-                                  ctypes.byref(missing), ctypes.byref(first), None), "adl_bloom_verify")
+                                  ctypes.byref(missing), ctypes.byref(first), _host_stream(stream)),
+           "adl_bloom_verify")
     return missing.value, (None if missing.value == 0 else first.value)
 
 
 # ------------------------------------------------------------------ synthetic inputs
 def synth_keys16(n: int, seed: int = 0x5EED, skip: int = 0, device="cuda", stream=None):
     """SURVEY.md §8d SplitMix64 16-byte keys generated on the device: (n,16) uint8."""
-    keys = _torch().empty((max(n, 1), 16), dtype=_torch().uint8, device=device)
+    with _on(stream):
+        keys = _torch().empty((max(n, 1), 16), dtype=_torch().uint8, device=device)
     _check(lib().adl_synth_keys16_device(_dptr(keys), seed, skip, n, _stream(stream)), "adl_synth_keys16_device")
     return keys[:n]
 
@@ -757,16 +802,18 @@ def synth_keys16(n: int, seed: int = 0x5EED, skip: int = 0, device="cuda", strea
 def synth_varlen(n: int, seed: int = 0x5EED, zipf_s: float = 1.1, device="cuda", stream=None):
     """Variable-length keys (8..256 B, Zipf lengths) on the device: (bytes, offsets[n+1] uint64)."""
     torch = _torch()
-    lengths = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-    _check(lib().adl_synth_varlen_lengths_device(_dptr(lengths), seed, n, zipf_s, _stream(stream)),
-           "adl_synth_varlen_lengths_device")
-    offs = torch.zeros(n + 1, dtype=torch.int64, device=device)
-    if n:
-        offs[1:] = torch.cumsum(lengths[:n].to(torch.int64), 0)
-    total = int(offs[-1].item())
-    data = torch.empty(((total + 15) // 16) * 16 + 16, dtype=torch.uint8, device=device)
-    _check(lib().adl_synth_varlen_fill_device(_dptr(data), seed, total, _stream(stream)),
-           "adl_synth_varlen_fill_device")
+    # the prefix sum between the two launches is torch's: it runs on `stream` too
+    with torch.cuda.stream(stream):
+        lengths = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        _check(lib().adl_synth_varlen_lengths_device(_dptr(lengths), seed, n, zipf_s, _stream(stream)),
+               "adl_synth_varlen_lengths_device")
+        offs = torch.zeros(n + 1, dtype=torch.int64, device=device)
+        if n:
+            offs[1:] = torch.cumsum(lengths[:n].to(torch.int64), 0)
+        total = int(offs[-1].item())
+        data = torch.empty(((total + 15) // 16) * 16 + 16, dtype=torch.uint8, device=device)
+        _check(lib().adl_synth_varlen_fill_device(_dptr(data), seed, total, _stream(stream)),
+               "adl_synth_varlen_fill_device")
     return data, offs  # int64 storage, read as uint64 offsets by the C-ABI
 
 
@@ -775,9 +822,10 @@ def synth_probe_queries(n: int, seed: int = 0xFEED, q0: int = 0, num_tables: int
     """Probe queries of BASELINE.json configs[4] on the device: (keys (n,16) u8, filter_id int32
     (read as uint32), member u8) -- see adl_synth_probe_queries_device."""
     torch = _torch()
-    keys = torch.empty((max(n, 1), 16), dtype=torch.uint8, device=device)
-    fid = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-    member = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
+    with _on(stream):
+        keys = torch.empty((max(n, 1), 16), dtype=torch.uint8, device=device)
+        fid = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        member = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
     _check(lib().adl_synth_probe_queries_device(_dptr(keys), _dptr(fid), _dptr(member), seed, q0, n, num_tables,
                                                 table_seed0, keys_per_table, _stream(stream)),
            "adl_synth_probe_queries_device")

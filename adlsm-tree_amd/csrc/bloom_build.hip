@@ -211,6 +211,12 @@ __global__ __launch_bounds__(256) void fill_maps_kernel(const FilterDesc *__rest
 // clears them before pass A).  Called by one thread; G % 8 == 0.
 constexpr uint32_t kQueueWords = 256;  // pass A's 8 counters, then pass B's, 64 B apart
 constexpr uint32_t kQueueMinItems = 16;  // items per workgroup below which a pass keeps the static order
+// Which table layout the workspace's last launch pair wrote: pass B leaves one of
+// these in a word of the queue block that no counter uses (the counters sit 16
+// words apart), where adl_bloom_build_positions reads it.  The layout depends
+// on the plan, the key shape and the flags; the workspace itself says which.
+constexpr uint32_t kLayoutWord = 8;
+constexpr uint32_t kLayoutDense = 0x4C594430u, kLayoutClaim = 0x4C594331u;
 struct GroupQueue {
   uint32_t *q;
   uint32_t G, total, g;
@@ -1135,6 +1141,7 @@ __global__ __launch_bounds__(BLK, 4 * OCC) void bloom_tile_kernel(BuildArgs a,
   constexpr int RPT = SEGB / BLK;  // table entries per thread per batch
   const uint32_t TL = a.TL;
   const uint32_t tile_words = 1u << (TL - 5);
+  if (blockIdx.x == 0 && tid == 0) scratch_ws[kLayoutWord] = a.claim ? kLayoutClaim : kLayoutDense;
   uint32_t *tile = lds;                                      // 2^TL bits
   uint2 *seg = reinterpret_cast<uint2 *>(lds + tile_words);  // SEGB {start word, length}
   uint32_t *qb = lds + tile_words + 2 * SEGB;                // DYN: 2 words, the tile after next
@@ -1564,10 +1571,6 @@ inline hipEvent_t *prof_slot() {
   return &t_prof.ev[4 * t_prof.used++];
 }
 
-// pass A of this thread's last launch pair wrote the claim layout's table
-// (adl_bloom_build_positions reads it)
-thread_local bool t_last_claim = false;
-
 template <bool DT, class Keys>
 int launch_binned_dt(const Plan &p, Keys keys, uint8_t *d_bitmaps, void *ws, hipStream_t st) {
   BuildArgs aa = p.a;
@@ -1688,7 +1691,6 @@ int launch_binned_dt(const Plan &p, Keys keys, uint8_t *d_bitmaps, void *ws, hip
   }
   BuildArgs ab = aa;
   ab.claim = claim_used;
-  t_last_claim = claim_used != 0;
   if (kn.debug)
     fprintf(stderr, "adl_bloom launch: pass A %s (%s, %s), pass B %s (%u per CU, %s)\n", a_queued ? "queued" : "static",
             a_kernel, DT ? "DT" : "kernarg", dyn_b ? "queued" : "static", p.occ_b, DT ? "DT" : "kernarg");
@@ -1882,16 +1884,24 @@ int adl_bloom_build_positions(const uint64_t *key_counts, uint32_t num_filters, 
       g = g0;
       g0 = e;
     }
-    hipStream_t st = adl_host::sync_stream(stream);
+    // The stream the *_device build given this `stream` ran on (NULL: the null
+    // stream), so the readback is ordered after that build.
+    hipStream_t st = (hipStream_t)stream;
     Plan p;
     if (int rc = make_plan(key_counts + g, num_filters - g, bits_per_key, p)) return rc;
     const uint32_t *tab = reinterpret_cast<const uint32_t *>(
                               adl_host::round_up(reinterpret_cast<uintptr_t>(d_workspace), 256)) +
                           p.pos_words;
+    // the layout of this workspace's table, as its own pass B recorded it
+    // (another build of this thread, on another workspace, does not change it)
+    uint32_t layout = 0;
+    ADL_HIP_TRY(hipMemcpyAsync(&layout, tab + p.table_words + kLayoutWord, 4, hipMemcpyDeviceToHost, st));
+    ADL_HIP_TRY(hipStreamSynchronize(st));
+    if (layout != kLayoutClaim && layout != kLayoutDense) return ADL_ERR_INVALID_ARG;  // no build has run in it
     uint64_t sum = 0;
     std::vector<uint32_t> row;
     for (const FilterDesc &d : p.f) {  // row T of each filter's table: every chunk's total
-      if (t_last_claim) {  // claim layout: the lengths in rows 0..T-1
+      if (layout == kLayoutClaim) {  // claim layout: the lengths in rows 0..T-1
         row.resize((uint64_t)d.tiles * d.chunks);
         if (row.empty()) continue;
         ADL_HIP_TRY(hipMemcpyAsync(row.data(), tab + d.table_base, row.size() * 4ull, hipMemcpyDeviceToHost, st));

@@ -477,9 +477,22 @@ int adl_bloom_profile_collect(double *ms, uint32_t *builds);
 int adl_bloom_profile_each(double *ms_ab, uint32_t capacity, uint32_t *launch_pairs);
 
 /* Bit-sets a build wrote as positions (pass A's output, after it skipped
- * repeated hash pairs), read back from the workspace of the last build made
- * with these key counts: *positions = the sum over its chunks.  For the
- * bench's traffic accounting (profiles/).  Synchronous on `stream`. */
+ * repeated hash pairs), read back from d_workspace, the workspace of a
+ * *_device build made with these key counts and bits_per_key: *positions =
+ * the sum over its chunks.  The build leaves the layout of its tables in the
+ * workspace itself, so the answer is that workspace's last build's whatever
+ * else the calling thread has built since, on this or another stream; a
+ * workspace no build has run in is ADL_ERR_INVALID_ARG.  `stream` means what
+ * it means to the *_device build (NULL = the null stream): pass the build's
+ * stream and the readback is ordered after the build with no synchronise in
+ * between.  Synchronous on `stream`.  For the bench's traffic accounting
+ * (profiles/).
+ * (Changed without a new ADL_BLOOM_ABI_VERSION, the signature and every
+ * structure being what they were: NULL used to mean the calling thread's own
+ * non-blocking stream here, which did not wait for a build on the null stream,
+ * and the layout used to be that of the calling thread's last build, so a
+ * workspace without a build was read as whatever that was instead of being
+ * refused.) */
 int adl_bloom_build_positions(const uint64_t *key_counts, uint32_t num_filters, int32_t bits_per_key,
                               const void *d_workspace, uint64_t *positions, void *stream);
 
