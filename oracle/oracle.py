@@ -6,7 +6,13 @@ container framing of the reference:
 
 * ``filter_block_final``  -- FilterBlockWriter::Final, src/filter_block.cpp:77-102
 * ``FilterBlockReaderOracle`` -- FilterBlockReader::Init / IsKeyExists,
-  src/filter_block.cpp:113-184
+  src/filter_block.cpp:113-184, with the further rejections of
+  adlsm-tree_amd/csrc/filter_block_format.hpp where the reference would read
+  outside the block
+
+``ref_lib`` and ``ref_filter_block_lib`` load the reference's own sources
+compiled into oracle/_ref/ (oracle/Makefile, target ref); tests/golden/ and
+tests/test_oracle_reference_cpu.py hold the restatement to them.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import
 this module.  The product (adlsm-tree_amd/) never does.
@@ -23,6 +29,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 _REF = None
+_REF_FB = None
 
 SEED1 = 0xE2C6928A  # src/filter_block.cpp:22
 SEED2 = 0xBAEA8A8F  # src/filter_block.cpp:23
@@ -91,6 +98,39 @@ def ref_lib():
                                         ctypes.c_void_p]
         _REF = L
     return _REF
+
+
+def ref_filter_block_lib():
+    """The reference's own src/filter_block.cpp (BloomFilter, FilterBlockWriter,
+    FilterBlockReader) behind oracle/ref_filter_block_harness.cpp, compiled into
+    oracle/_ref/ (None if absent)."""
+    global _REF_FB
+    if _REF_FB is None:
+        path = os.path.join(HERE, "_ref", "libref_filter_block.so")
+        if not os.path.exists(path):
+            return None
+        L = ctypes.CDLL(path)
+        vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32
+        L.ref_code_outside.restype = ctypes.c_int
+        L.ref_code_outside.argtypes = []
+        L.ref_code_div_zero.restype = ctypes.c_int
+        L.ref_code_div_zero.argtypes = []
+        L.ref_keys2block.restype = ctypes.c_int64
+        L.ref_keys2block.argtypes = [ctypes.c_int, vp, vp, u64, vp, u64]
+        L.ref_is_key_exists.restype = ctypes.c_int
+        L.ref_is_key_exists.argtypes = [ctypes.c_int, ctypes.c_char_p, u64, vp, u64]
+        L.ref_is_key_exists_batch.restype = ctypes.c_int
+        L.ref_is_key_exists_batch.argtypes = [ctypes.c_int, vp, vp, u64, vp, u64, vp]
+        L.ref_filter_block_build.restype = ctypes.c_int64
+        L.ref_filter_block_build.argtypes = [ctypes.c_int, vp, vp, vp, ctypes.c_uint32, vp, u64]
+        L.ref_reader_init.restype = ctypes.c_int
+        L.ref_reader_init.argtypes = [vp, u64]
+        L.ref_reader_is_key_exists.restype = ctypes.c_int
+        L.ref_reader_is_key_exists.argtypes = [vp, u64, i32, ctypes.c_char_p, u64]
+        L.ref_reader_is_key_exists_batch.restype = ctypes.c_int
+        L.ref_reader_is_key_exists_batch.argtypes = [vp, u64, vp, vp, vp, u64, vp]
+        _REF_FB = L
+    return _REF_FB
 
 
 def _ptr(a):
@@ -275,8 +315,26 @@ class FilterBlockReaderOracle:
             return FILTER_BLOCK_ERROR
         if self.offsets_off + 4 > L:
             return FILTER_BLOCK_ERROR  # reference reads out of bounds here (UB)
+        # The reference trusts the rest (its IsKeyExists then reads outside the
+        # block); adlsm-tree_amd/csrc/filter_block_format.hpp does not: the
+        # offsets array lies inside the block, before the count field ...
+        nf = self.filters_nums
+        if nf < 0 or self.offsets_off + 4 * (nf if nf else 1) > nums_off:
+            return FILTER_BLOCK_ERROR
         (zero,) = struct.unpack_from("<i", b, self.offsets_off)
         if zero != 0:
+            return FILTER_BLOCK_ERROR
+        # ... its entries are in order and none lies beyond offsets_start, and
+        # no filter has more than 2^31 bits (the reference's `int` m, :50)
+        prev = 0
+        for f in range(nf):
+            (o,) = struct.unpack_from("<i", b, self.offsets_off + 4 * f)
+            if o < 0 or o > self.offsets_off or o < prev:
+                return FILTER_BLOCK_ERROR
+            if f and (o - prev) * 8 > 0x7FFFFFFF:
+                return FILTER_BLOCK_ERROR
+            prev = o
+        if nf and (self.offsets_off - prev) * 8 > 0x7FFFFFFF:
             return FILTER_BLOCK_ERROR
         return 0
 
@@ -293,6 +351,10 @@ class FilterBlockReaderOracle:
         if i >= self.filters_nums or i < 0:
             return False
         o1, o2 = self.filter_range(i)
+        if o1 == o2:
+            # an empty range: the reference computes h % 0 (:56); the product answers 0
+            # (adlsm-tree_amd/csrc/probe_device.hpp)
+            return False
         bm = np.frombuffer(self.block[o1:o2], dtype=np.uint8)
         return bool(probe([bytes(key)], bm, bits_per_key=self.bits_per_key)[0])
 
