@@ -51,6 +51,9 @@ EXPORTS = (
     "adl_bloom_filter_cache_build", "adl_bloom_filter_cache_build_workspace_bytes",
     "adl_bloom_filter_cache_build_device", "adl_bloom_filter_cache_publish", "adl_bloom_filter_cache_abandon",
     "adl_bloom_verify_device", "adl_bloom_verify",
+    "adl_bloom_level_create", "adl_bloom_level_destroy", "adl_bloom_level_stats",
+    "adl_bloom_level_candidates_workspace_bytes",
+    "adl_bloom_level_candidates_device", "adl_bloom_level_multiget",
 )
 
 _LIB = None
@@ -110,6 +113,15 @@ def lib() -> ctypes.CDLL:
         "adl_bloom_verify_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, i32, vp, vp]),
         "adl_bloom_verify": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, i32, ctypes.POINTER(u64),
                                              ctypes.POINTER(u64), vp]),
+        "adl_bloom_level_create": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, u32, u64, ctypes.POINTER(vp)]),
+        "adl_bloom_level_destroy": (ctypes.c_int, [vp]),
+        "adl_bloom_level_stats": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                                  ctypes.POINTER(u32)]),
+        "adl_bloom_level_candidates_workspace_bytes": (u64, [u64]),
+        "adl_bloom_level_candidates_device": (ctypes.c_int, [vp, vp, vp, u64, u32, ctypes.c_int64, vp, vp, u64, vp,
+                                                              vp, u64, vp]),
+        "adl_bloom_level_multiget": (ctypes.c_int, [vp, vp, u32, vp, vp, u64, u32, ctypes.c_int64, vp, vp, vp, u64,
+                                                     ctypes.POINTER(u64), ctypes.POINTER(u64), vp]),
         "adl_bloom_probe_device": (ctypes.c_int, [vp, vp, u64, u32, i32, vp, u64, vp, vp]),
         "adl_bloom_probe_batch_workspace_bytes": (u64, [u64, u32, i32, u32]),
         "adl_bloom_probe_batch_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, i32, vp, vp, u64, vp]),
@@ -757,6 +769,109 @@ class FilterCache:
     def close(self):
         if self._h:
             lib().adl_bloom_filter_cache_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ADL_ERR_TOO_LARGE = -2
+ADL_ERR_WORKSPACE = -5
+
+
+def _ptr_array(items):
+    """list[bytes] -> (char*[] kept alive by the caller, lengths u64)."""
+    arr = (ctypes.c_char_p * max(len(items), 1))(*items)
+    return arr, np.array([len(b) for b in items] or [0], dtype=np.uint64)
+
+
+class LevelIndex:
+    """A level's resident index (adl_bloom_level): built once from the tables' (min, max) inner keys,
+    asked about many times.  tables: [(min_inner_key, max_inner_key)]; oids: their cache keys (needed by
+    multiget only).  Raises AdlBloomError(ADL_ERR_TOO_LARGE) when the index would exceed max_index_bytes
+    (0: 256 MiB)."""
+
+    def __init__(self, tables, oids=None, max_index_bytes: int = 0):
+        self._h = ctypes.c_void_p()
+        self.num_tables = len(tables)
+        mins, ml = _ptr_array([bytes(t[0]) for t in tables])
+        maxs, xl = _ptr_array([bytes(t[1]) for t in tables])
+        po, ol = (None, None) if oids is None else _ptr_array([bytes(o) for o in oids])
+        if oids is not None and len(oids) != len(tables):
+            raise ValueError("one oid per table")
+        _check(lib().adl_bloom_level_create(None if po is None else ctypes.cast(po, ctypes.c_void_p),
+                                            None if ol is None else ol.ctypes.data,
+                                            ctypes.cast(mins, ctypes.c_void_p), ml.ctypes.data,
+                                            ctypes.cast(maxs, ctypes.c_void_p), xl.ctypes.data, len(tables),
+                                            max_index_bytes, ctypes.byref(self._h)), "adl_bloom_level_create")
+
+    def stats(self):
+        """-> (regions, list entries, device bytes, longest candidate list)."""
+        r, lg = ctypes.c_uint32(), ctypes.c_uint32()
+        e, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().adl_bloom_level_stats(self._h, ctypes.byref(r), ctypes.byref(e), ctypes.byref(b),
+                                           ctypes.byref(lg)), "adl_bloom_level_stats")
+        return r.value, e.value, b.value, lg.value
+
+    @staticmethod
+    def _host_keys(keys, offsets):
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        if offsets is None:
+            n, stride, po = keys.shape[0], keys.shape[1], None
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            n, stride, po = len(offsets) - 1, 0, offsets.ctypes.data
+        kp = keys.ctypes.data if keys.size else np.zeros(16, np.uint8).ctypes.data
+        return (keys, offsets), kp, po, n, stride
+
+    def candidates_device(self, keys, offsets=None, seq: int = 2**63 - 1, pair_capacity: int | None = None,
+                          stream=None):
+        """Selection on the device from torch device tensors, enqueued on `stream` without a synchronise:
+        (pair_begin int32[n+1], pair_table int32[pair_capacity], num_pairs int64[1]) device tensors, read as
+        unsigned.  pair_capacity: default n * the longest list."""
+        torch = _torch()
+        pk, po, n, stride = _keyset(keys, offsets)
+        cap = n * self.stats()[3] if pair_capacity is None else int(pair_capacity)
+        wsb = lib().adl_bloom_level_candidates_workspace_bytes(n)
+        with _on(stream):
+            pb = torch.empty(n + 1, dtype=torch.int32, device=keys.device)
+            pt = torch.empty(max(cap, 1), dtype=torch.int32, device=keys.device)
+            npairs = torch.empty(1, dtype=torch.int64, device=keys.device)
+            ws = empty_device(wsb, keys.device)
+        _check(lib().adl_bloom_level_candidates_device(self._h, pk, po, n, stride, seq, _dptr(pb), _dptr(pt), cap,
+                                                       _dptr(npairs), _dptr(ws), wsb, _stream(stream)),
+               "adl_bloom_level_candidates_device")
+        return pb, pt[:cap], npairs
+
+    def multiget_status(self, cache: "FilterCache", keys: np.ndarray, offsets=None, seq: int = 2**63 - 1,
+                        filter: int = 0, pair_capacity: int | None = None, stream=None):
+        """adl_bloom_level_multiget: (status, pair_begin, pair_table, answers, num_pairs, uncached)."""
+        keep, kp, po, n, stride = self._host_keys(keys, offsets)
+        cap = n * self.stats()[3] if pair_capacity is None else int(pair_capacity)
+        pb = np.zeros(n + 1, dtype=np.uint32)
+        pt = np.zeros(max(cap, 1), dtype=np.uint32)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        npairs, unc = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = lib().adl_bloom_level_multiget(self._h, cache._h, filter, kp, po, n, stride, seq, pb.ctypes.data,
+                                            pt.ctypes.data, out.ctypes.data, cap, ctypes.byref(npairs),
+                                            ctypes.byref(unc), _host_stream(stream))
+        m = min(npairs.value, cap)
+        return rc, pb, pt[:m], out[:m], npairs.value, unc.value
+
+    def multiget(self, cache: "FilterCache", keys: np.ndarray, offsets=None, seq: int = 2**63 - 1, filter: int = 0,
+                 stream=None):
+        """Level multi-get: keys up; selection, expansion and probes on the device;
+        (pair_begin, pair_table, answers, uncached) back."""
+        rc, pb, pt, out, _, unc = self.multiget_status(cache, keys, offsets, seq, filter, None, stream)
+        _check(rc, "adl_bloom_level_multiget")
+        return pb, pt, out, unc
+
+    def close(self):
+        if self._h:
+            lib().adl_bloom_level_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

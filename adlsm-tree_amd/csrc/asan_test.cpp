@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "filter_block.hpp"
+#include "level_filter.hpp"
 #include "filter_block_format.hpp"
 #include "sstable_writer.hpp"
 
@@ -210,11 +211,67 @@ void WriterChecks() {
         (unsigned char)file[file.size() - 1] == 0x34);  // footer magic (src/footer_block.cpp:24-25)
 }
 
+// The level index builder and its host lookup (level_index_core.hpp through
+// LevelIndex and LevelCandidates): empty levels, empty and repeated keys,
+// tables whose max sorts before their min, inner keys without a suffix, a
+// budget that refuses the index.  Every lookup equals TableCoversKey on every
+// table, in LevelCandidates' order.
+void LevelIndexChecks() {
+  auto inner = [](const std::string &user, int64_t seq, char op) {
+    std::string k = user;
+    k.append(reinterpret_cast<const char *>(&seq), 8);
+    k.push_back(op);
+    return k;
+  };
+  const std::vector<std::string> users = {"", "a", "ab", std::string("ab\0", 3), "b", std::string(40, 'p'),
+                                          std::string(40, 'p') + "\x80", "\x7f\x10", "\x80\x01", "\xff"};
+  uint64_t s = 0x5A17;
+  auto rnd = [&](uint64_t n) {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    return (s >> 33) % n;
+  };
+  for (int round = 0; round < 40; ++round) {
+    std::vector<TableRange> tabs(round == 0 ? 0 : 1 + rnd(12));
+    for (auto &t : tabs) {
+      const std::string &a = users[rnd(users.size())], &b = users[rnd(users.size())];
+      t.oid = "t";
+      t.min_inner_key = rnd(5) ? inner(a, (int64_t)rnd(4), (char)rnd(2)) : a.substr(0, 8);
+      t.max_inner_key = rnd(5) ? inner(b, (int64_t)rnd(4), (char)rnd(2)) : b.substr(0, 8);
+    }
+    LevelIndex index(tabs);
+    CHECK(index.status() == OK);
+    std::vector<std::string> keys(users);
+    keys.push_back(std::string(300, 'z'));
+    keys.push_back("a" + std::string(1, '\0'));
+    std::vector<std::string_view> kv(keys.begin(), keys.end());
+    for (int64_t seq : {(int64_t)0, (int64_t)2, INT64_MAX}) {
+      std::vector<uint32_t> b1, t1, b2, t2;
+      index.Candidates(kv, seq, b1, t1);
+      LevelCandidates(tabs, kv, seq, b2, t2);
+      CHECK(b1 == b2 && t1 == t2);
+      for (size_t i = 0; i < kv.size(); ++i) {
+        size_t covered = 0;
+        for (const auto &t : tabs) covered += TableCoversKey(t, kv[i], seq);
+        CHECK(b1[i + 1] - b1[i] == covered);
+      }
+    }
+  }
+  // 64 mutually overlapping tables: a 4 KiB budget refuses the index
+  std::vector<TableRange> wide(64);
+  for (int t = 0; t < 64; ++t) {
+    wide[t].min_inner_key = inner("u" + std::to_string(100 + t), 1, 0);
+    wide[t].max_inner_key = inner("v" + std::to_string(100 + t), 1, 0);
+  }
+  CHECK(LevelIndex(wide, 4096).status() == OUT_OF_RANGE);
+  CHECK(LevelIndex(wide).status() == OK && LevelIndex(wide).longest_list() == 64);
+}
+
 }  // namespace
 
 int main() {
   ParserChecks();
   WriterChecks();
+  LevelIndexChecks();
   printf("asan_test: %d failed checks\n", g_fail);
   return g_fail ? 1 : 0;
 }

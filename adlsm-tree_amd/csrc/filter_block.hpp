@@ -235,6 +235,8 @@ class FilterCache {
    * kept until exit.  (Shared(int) is the round-5 spelling: the same cache.) */
   static FilterCache *Shared();
   static FilterCache *Shared(int bits_per_key);
+  /* the C-ABI handle (NULL when creation failed), for calls that take a cache */
+  adl_bloom_filter_cache *handle() const { return h_; }
 
  private:
   adl_bloom_filter_cache *h_ = nullptr;

@@ -53,6 +53,7 @@
 #include "bloom_common.hpp"
 #include "filter_block_format.hpp"
 #include "filter_cache_impl.hpp"
+#include "level_index_impl.hpp"
 #include "probe_server.hpp"
 
 namespace {
@@ -525,6 +526,117 @@ int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *c, const char *c
     unpin_tables(c, res);
     if (rc) return rc;
     memcpy(h_out, hbuf + o_out, np);
+    if (h_uncached) *h_uncached = uncached;
+    return ADL_OK;
+  } catch (...) {
+    return ADL_ERR_OUT_OF_MEMORY;
+  }
+}
+
+// The level multi-get over a resident index (level_index.hip): keys and
+// offsets up, selection + expansion + fan-out probe on the device, the begin
+// entries, table indices and answers down.  The level's tables are resolved
+// and pinned exactly as adl_bloom_filter_cache_probe_fanout resolves its oid
+// list, so the answers are that call's on the same lists.
+int adl_bloom_level_multiget(adl_bloom_level *lv, adl_bloom_filter_cache *c, uint32_t filter, const uint8_t *h_keys,
+                             const uint64_t *h_offsets, uint64_t num_keys, uint32_t key_stride, int64_t seq,
+                             uint32_t *h_pair_begin, uint32_t *h_pair_table, uint8_t *h_out, uint64_t pair_capacity,
+                             uint64_t *num_pairs, uint64_t *h_uncached, void *stream) {
+  if (!lv || !c || !num_pairs || !h_pair_begin) return ADL_ERR_INVALID_ARG;
+  *num_pairs = 0;
+  if (h_uncached) *h_uncached = 0;
+  h_pair_begin[0] = 0;
+  if (num_keys == 0) return ADL_OK;
+  const uint32_t num_tables = lv->ix.num_tables;
+  if (!h_keys || (!h_offsets && key_stride == 0) || (pair_capacity && (!h_pair_table || !h_out)))
+    return ADL_ERR_INVALID_ARG;
+  if (num_tables && lv->oids.size() != num_tables) return ADL_ERR_INVALID_ARG;  // created without oids
+  if (num_keys >= 0xffffffffull) return ADL_ERR_TOO_LARGE;
+  try {
+    hipStream_t st = adl_host::sync_stream(stream);
+    const uint64_t cap = std::min<uint64_t>(pair_capacity, 0xffffffffull);
+    // 1. under the lock: the level's tables' ranges and k, pinned and marked used
+    Resolved &res = t_res;
+    {
+      std::vector<const char *> op(num_tables);
+      std::vector<uint64_t> ol(num_tables);
+      for (uint32_t t = 0; t < num_tables; ++t) {
+        op[t] = lv->oids[t].data();
+        ol[t] = lv->oids[t].size();
+      }
+      resolve_tables(c, op.data(), ol.data(), num_tables, filter, res);
+    }
+    // 2. without the lock: keys, offsets and the range and k tables in one H2D;
+    //    selection (three launches) and the fan-out probe; then the results
+    const uint64_t key_bytes = h_offsets ? h_offsets[num_keys] : num_keys * (uint64_t)key_stride;
+    const uint64_t off_bytes = h_offsets ? (num_keys + 1) * 8 : 0;
+    const uint64_t wsb = adl_bloom_level_candidates_workspace_bytes(num_keys);
+    const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
+    const uint64_t o_be = o_offs + adl_host::round_up(off_bytes, 256);
+    const uint64_t o_k = o_be + adl_host::round_up(res.be.size() * 8, 256);
+    const uint64_t o_np = o_k + adl_host::round_up(num_tables, 256);  // end of the upload
+    const uint64_t o_pb = o_np + 256;
+    const uint64_t o_pt = o_pb + adl_host::round_up((num_keys + 1) * 4, 256);
+    const uint64_t o_out = o_pt + adl_host::round_up(cap * 4, 256);
+    const uint64_t o_ws = o_out + adl_host::round_up(cap, 256);
+    const uint64_t total = o_ws + wsb;
+    adl_host::Staging &sg = adl_host::t_stage;
+    int rc = sg.reserve(o_ws, total);
+    uint8_t *hbuf = sg.host, *dbuf = sg.dev;
+    uint64_t np = 0;
+    if (rc == ADL_OK) {
+      if (key_bytes) memcpy(hbuf, h_keys, key_bytes);
+      if (off_bytes) memcpy(hbuf + o_offs, h_offsets, off_bytes);
+      memcpy(hbuf + o_be, res.be.data(), res.be.size() * 8);
+      if (num_tables) memcpy(hbuf + o_k, res.kt.data(), num_tables);
+      if (hipMemcpyAsync(dbuf, hbuf, o_np, hipMemcpyHostToDevice, st) != hipSuccess) rc = ADL_ERR_DEVICE;
+    }
+    const uint64_t *d_offs = h_offsets ? reinterpret_cast<const uint64_t *>(dbuf + o_offs) : nullptr;
+    uint32_t *d_pb = reinterpret_cast<uint32_t *>(dbuf + o_pb), *d_pt = reinterpret_cast<uint32_t *>(dbuf + o_pt);
+    if (rc == ADL_OK)
+      rc = adl_host::level_select_device(lv, dbuf, d_offs, num_keys, key_stride, seq, d_pb, d_pt, cap,
+                                         reinterpret_cast<uint64_t *>(dbuf + o_np), dbuf + o_ws, wsb, st);
+    if (rc == ADL_OK && cap) {
+      // (the kernel stops at cap pairs whatever pair_begin says)
+      const uint64_t *d_be = reinterpret_cast<const uint64_t *>(dbuf + o_be);
+      rc = adl_host::adl_probe_fanout_device_ev(dbuf, d_offs, num_keys, key_stride, d_pb, d_pt, cap, num_tables,
+                                                c->arena, d_be, d_be + num_tables, dbuf + o_k, dbuf + o_out, st,
+                                                nullptr);
+    }
+    // A batch whose whole result area is small comes back in one copy; a
+    // larger one first learns how many pairs there are.
+    const bool one_copy = o_ws - o_np <= (256u << 10);
+    if (rc == ADL_OK &&
+        hipMemcpyAsync(hbuf + o_np, dbuf + o_np, one_copy ? o_ws - o_np : o_pt - o_np, hipMemcpyDeviceToHost, st) !=
+            hipSuccess)
+      rc = ADL_ERR_DEVICE;
+    if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
+    if (rc == ADL_OK) {
+      memcpy(&np, hbuf + o_np, 8);
+      const uint64_t have = std::min(np, cap);
+      if (!one_copy && have) {
+        if (hipMemcpyAsync(hbuf + o_pt, dbuf + o_pt, have * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(hbuf + o_out, dbuf + o_out, have, hipMemcpyDeviceToHost, st) != hipSuccess)
+          rc = ADL_ERR_DEVICE;
+        if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
+      }
+    }
+    // 3. the kernels and the copies are done: unpin
+    uint64_t uncached = 0;
+    if (rc == ADL_OK && np <= cap) {
+      const uint32_t *pt = reinterpret_cast<const uint32_t *>(hbuf + o_pt);
+      for (uint64_t p = 0; p < np; ++p) uncached += !res.cached[pt[p]];
+    }
+    unpin_tables(c, res);
+    if (rc) return rc;
+    *num_pairs = np;
+    if (np > 0xffffffffull) return ADL_ERR_TOO_LARGE;
+    memcpy(h_pair_begin, hbuf + o_pb, (num_keys + 1) * 4);
+    if (np > pair_capacity) return ADL_ERR_WORKSPACE;
+    if (np) {
+      memcpy(h_pair_table, hbuf + o_pt, np * 4);
+      memcpy(h_out, hbuf + o_out, np);
+    }
     if (h_uncached) *h_uncached = uncached;
     return ADL_OK;
   } catch (...) {

@@ -8,40 +8,16 @@
 #include <algorithm>
 #include <numeric>
 
+#include "adl_bloom.h"
+#include "level_index_core.hpp"
+
 namespace adl {
 
 namespace {
 
-/* An inner key decoded as MemKey::FromKey does (src/keys.cpp:86-91); keys
- * shorter than the 9-byte suffix compare as (whole key, seq 0, op 0). */
-struct Decoded {
-  string_view user;
-  int64_t seq = 0;
-  int op = 0;
-};
-
-Decoded Decode(string_view k) {
-  Decoded d;
-  if (k.size() < 9) {
-    d.user = k;
-    return d;
-  }
-  d.user = k.substr(0, k.size() - 9);
-  memcpy(&d.seq, k.data() + k.size() - 9, 8);
-  d.op = (unsigned char)k[k.size() - 1];
-  return d;
-}
-
-/* MemKey::operator< (src/keys.cpp:61-74) */
-bool Less(const Decoded &a, const Decoded &b) {
-  const int cmp = a.user.compare(b.user);
-  if (cmp < 0) return true;
-  if (cmp == 0) {
-    if (a.seq > b.seq) return true;
-    if (a.seq == b.seq && a.op > b.op) return true;
-  }
-  return false;
-}
+using adl_level::Decode;
+using adl_level::Decoded;
+using adl_level::Less;
 
 }  // namespace
 
@@ -70,6 +46,10 @@ void LevelCandidates(const vector<TableRange> &tables, const vector<string_view>
   const size_t K = user_keys.size(), T = tables.size();
   begin.assign(K + 1, 0);
   table.clear();
+  // The per-call form of the region index: sorted, swept and searched for this
+  // one batch at this one seq.  A caller that asks about the same level again
+  // keeps a LevelIndex (level_index_core.hpp), which builds the same regions
+  // once, independent of seq.
   // files_meta_ order (ascending min_inner_key, stable), visited in reverse
   vector<uint32_t> asc(T);
   std::iota(asc.begin(), asc.end(), 0u);
@@ -236,15 +216,35 @@ int LevelFanout() {
  * 1.3 (224 KB saved). */
 constexpr int64_t kFanoutMinSavedBytes = 32 << 10;
 
-}  // namespace
+/* ADL_BLOOM_LEVEL_DEVICE_MIN_KEYS, read once per process: the
+ * batch size from which LevelMultiGetFilter(cache, LevelIndex, ...) selects on
+ * the device; 0 = never.  The default is the measured crossover (DESIGN.md §5,
+ * "Resident level index"): the device path costs 40-60 us up to a few thousand
+ * keys, so on 16-table levels it loses 12-16 us to the host copy at 1 000 keys
+ * and 2-11 us at 2 000, wins on every level measured at 3 000 (by 1-11 us) and
+ * at 4 000 (7-23 us), and is 3-4x faster at 65 536. */
+constexpr uint64_t kLevelDeviceMinKeys = 3000;
 
-RC LevelMultiGetFilter(FilterCache &cache, const vector<TableRange> &tables, const vector<string_view> &user_keys,
-                       int64_t seq, MultiGetFilterResult &out) {
-  out = MultiGetFilterResult{};
-  LevelCandidates(tables, user_keys, seq, out.begin, out.table);
-  const size_t T = tables.size(), K = user_keys.size();
-  vector<string_view> oids(T);
-  for (size_t t = 0; t < T; ++t) oids[t] = tables[t].oid;
+uint64_t LevelDeviceMinKeys() {
+  static const uint64_t v = [] {
+    const char *e = getenv("ADL_BLOOM_LEVEL_DEVICE_MIN_KEYS");
+    return e && *e ? (uint64_t)strtoull(e, nullptr, 10) : kLevelDeviceMinKeys;
+  }();
+  return v;
+}
+
+RC FromStatus(int status) {
+  if (status == ADL_OK) return OK;
+  if (status == ADL_FILTER_BLOCK_ERROR) return FILTER_BLOCK_ERROR;
+  if (status == ADL_ERR_TOO_LARGE) return OUT_OF_RANGE;
+  return DEVICE_ERROR;
+}
+
+/* The probes of a selected batch: out.begin / out.table are key i's candidates;
+ * fills out.maybe and out.uncached. */
+RC ProbeSelected(FilterCache &cache, const vector<string_view> &oids, const vector<string_view> &user_keys,
+                 MultiGetFilterResult &out) {
+  const size_t K = user_keys.size();
   // SSTableReader::Get probes the user key (src/sstable.cpp:238).  Upload per
   // path: a batch of pairs carries key bytes + an 8-byte offset + a table id
   // per PAIR; the fan-out batch carries key bytes + offset + a begin entry
@@ -271,6 +271,123 @@ RC LevelMultiGetFilter(FilterCache &cache, const vector<TableRange> &tables, con
   return cache.Probe(oids, out.table, batch, 0, out.maybe, &out.uncached);
 }
 
+}  // namespace
+
+RC LevelMultiGetFilter(FilterCache &cache, const vector<TableRange> &tables, const vector<string_view> &user_keys,
+                       int64_t seq, MultiGetFilterResult &out) {
+  out = MultiGetFilterResult{};
+  LevelCandidates(tables, user_keys, seq, out.begin, out.table);
+  const size_t T = tables.size();
+  vector<string_view> oids(T);
+  for (size_t t = 0; t < T; ++t) oids[t] = tables[t].oid;
+  return ProbeSelected(cache, oids, user_keys, out);
+}
+
+LevelIndex::LevelIndex(const vector<TableRange> &tables, uint64_t max_index_bytes)
+    : ix_(new adl_level::Index), tables_(tables), max_index_bytes_(max_index_bytes) {
+  const size_t T = tables_.size();
+  vector<string_view> mins(T), maxs(T);
+  oid_views_.resize(T);
+  for (size_t t = 0; t < T; ++t) {
+    oid_views_[t] = tables_[t].oid;
+    mins[t] = tables_[t].min_inner_key;
+    maxs[t] = tables_[t].max_inner_key;
+  }
+  status_ = adl_level::Build(mins.data(), maxs.data(), T,
+                             max_index_bytes ? max_index_bytes : adl_level::kDefaultIndexBytes, *ix_)
+                ? OK
+                : OUT_OF_RANGE;
+}
+
+LevelIndex::~LevelIndex() { (void)adl_bloom_level_destroy(h_); }
+
+uint32_t LevelIndex::longest_list() const { return ix_->longest; }
+
+uint32_t LevelIndex::mean_list() const {
+  const uint64_t regions = 2ull * ix_->num_boundaries + 1;
+  return (uint32_t)((ix_->rlist.size() + regions - 1) / regions);
+}
+
+adl_bloom_level *LevelIndex::handle() {
+  std::call_once(handle_once_, [this] {
+    if (status_) {
+      device_status_ = status_;
+      return;
+    }
+    const size_t T = tables_.size();
+    vector<const char *> op(T), mn(T), mx(T);
+    vector<uint64_t> ol(T), ml(T), xl(T);
+    for (size_t t = 0; t < T; ++t) {
+      op[t] = tables_[t].oid.data();
+      ol[t] = tables_[t].oid.size();
+      mn[t] = tables_[t].min_inner_key.data();
+      ml[t] = tables_[t].min_inner_key.size();
+      mx[t] = tables_[t].max_inner_key.data();
+      xl[t] = tables_[t].max_inner_key.size();
+    }
+    device_status_ = FromStatus(adl_bloom_level_create(op.data(), ol.data(), mn.data(), ml.data(), mx.data(),
+                                                       xl.data(), (uint32_t)T, max_index_bytes_, &h_));
+  });
+  return h_;
+}
+
+void LevelIndex::Candidates(const vector<string_view> &user_keys, int64_t seq, vector<uint32_t> &begin,
+                            vector<uint32_t> &table) const {
+  const size_t K = user_keys.size();
+  begin.assign(K + 1, 0);
+  table.clear();
+  if (status_) return;
+  adl_level::Lookup(*ix_, K, [&](size_t i) { return user_keys[i]; }, seq, begin.data(), table);
+}
+
+RC LevelMultiGetFilter(FilterCache &cache, LevelIndex &level, const vector<string_view> &user_keys, int64_t seq,
+                       MultiGetFilterResult &out) {
+  out = MultiGetFilterResult{};
+  if (level.status()) return level.status();
+  const size_t K = user_keys.size();
+  const uint64_t min_keys = LevelDeviceMinKeys();
+  if (min_keys == 0 || K < min_keys) {
+    // the call above without its per-call index build
+    level.Candidates(user_keys, seq, out.begin, out.table);
+    return ProbeSelected(cache, level.oids(), user_keys, out);
+  }
+  adl_bloom_level *lv = level.handle();
+  if (!lv) return level.device_status();
+  if (!cache.handle()) return cache.status();
+  // keys up, lists and answers down: selection, expansion and the probes on
+  // the device.
+  size_t key_bytes = 0;
+  for (string_view k : user_keys) key_bytes += k.size();
+  KeyArena batch;
+  batch.Reserve(K, key_bytes);
+  for (string_view k : user_keys) batch.Add(k);
+  // No key has more than longest_list() candidates, but one wide region must
+  // not size every batch's buffers (here and, pinned, in the library) for
+  // K x longest: room for twice the mean list per key first, and the exact
+  // size, which the call reports, where a batch needs more.
+  const uint64_t worst = std::min<uint64_t>((uint64_t)K * level.longest_list(), 0xffffffffull);
+  uint64_t cap = std::min<uint64_t>(worst, 2ull * K * level.mean_list() + 1024);
+  out.begin.assign(K + 1, 0);
+  uint64_t np = 0;
+  int st = ADL_OK;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    out.table.resize(cap);
+    out.maybe.resize(cap);
+    st = adl_bloom_level_multiget(lv, cache.handle(), 0, reinterpret_cast<const uint8_t *>(batch.bytes().data()),
+                                  batch.offsets().data(), K, 0, seq, out.begin.data(), out.table.data(),
+                                  out.maybe.data(), cap, &np, &out.uncached, nullptr);
+    if (st != ADL_ERR_WORKSPACE || np <= cap || np > worst) break;
+    cap = np;
+  }
+  if (st != ADL_OK) {
+    out = MultiGetFilterResult{};
+    return FromStatus(st);
+  }
+  out.table.resize(np);
+  out.maybe.resize(np);
+  return OK;
+}
+
 }  // namespace adl
 
 /* Test hook (tests/test_level_cpu.py): LevelCandidates over tables and keys
@@ -293,4 +410,36 @@ extern "C" int64_t adl_level_candidates(const char *const *mins, const uint64_t 
   std::copy(b.begin(), b.end(), begin);
   std::copy(tb.begin(), tb.end(), table);
   return (int64_t)tb.size();
+}
+
+/* Test hook (tests/test_level_index_cpu.py): ONE LevelIndex over the tables,
+ * then `batches` host lookups in it, batch b = keys [key_begin[b],
+ * key_begin[b+1]) at seqs[b].  begin: one entry per key and one more per
+ * batch, batch b's starting at key_begin[b] + b and counting from 0; table:
+ * the lists of all batches back to back, up to cap entries.  Returns the
+ * number of pairs, -1 when cap is too small, -2 when the index was not built. */
+extern "C" int64_t adl_level_index_candidates(const char *const *mins, const uint64_t *min_lens,
+                                              const char *const *maxs, const uint64_t *max_lens, uint32_t T,
+                                              uint64_t max_index_bytes, const char *const *keys,
+                                              const uint64_t *key_lens, const uint32_t *key_begin, uint32_t batches,
+                                              const int64_t *seqs, uint32_t *begin, uint32_t *table, uint64_t cap) {
+  std::vector<adl::TableRange> tabs(T);
+  for (uint32_t t = 0; t < T; ++t) {
+    tabs[t].min_inner_key.assign(mins[t], min_lens[t]);
+    tabs[t].max_inner_key.assign(maxs[t], max_lens[t]);
+  }
+  adl::LevelIndex index(tabs, max_index_bytes);
+  if (index.status()) return -2;
+  uint64_t total = 0;
+  for (uint32_t b = 0; b < batches; ++b) {
+    std::vector<std::string_view> ks;
+    for (uint32_t i = key_begin[b]; i < key_begin[b + 1]; ++i) ks.emplace_back(keys[i], key_lens[i]);
+    std::vector<uint32_t> bg, tb;
+    index.Candidates(ks, seqs[b], bg, tb);
+    if (total + tb.size() > cap) return -1;
+    std::copy(bg.begin(), bg.end(), begin + key_begin[b] + b);
+    std::copy(tb.begin(), tb.end(), table + total);
+    total += tb.size();
+  }
+  return (int64_t)total;
 }

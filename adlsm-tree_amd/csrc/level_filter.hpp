@@ -19,12 +19,19 @@
 #pragma once
 #include <stdint.h>
 
+#include <memory>
+#include <mutex>
 #include <string>
 #include <string_view>
 #include <vector>
 
 #include "filter_block.hpp"
 #include "rc.hpp"
+
+struct adl_bloom_level;
+namespace adl_level {
+struct Index;
+}
 
 namespace adl {
 
@@ -76,5 +83,64 @@ void LevelCandidates(const vector<TableRange> &tables, const vector<string_view>
 
 RC LevelMultiGetFilter(FilterCache &cache, const vector<TableRange> &tables, const vector<string_view> &user_keys,
                        int64_t seq, MultiGetFilterResult &out);
+
+/* A level described ONCE, where its revision installs it, and asked about many
+ * times: the region index LevelCandidates builds per call (boundary user
+ * keys, per region the candidate tables in visiting order; see
+ * level_index_core.hpp), kept on the host and -- from the first device
+ * multi-get on, as an adl_bloom_level of the C-ABI -- on the device.  It does
+ * not depend on a lookup's seq.  Immutable, so any number of threads may look
+ * keys up in it at once.  Drop it with the revision.
+ *
+ * Host memory: the index, plus a copy of the tables' oids and ranges.  The
+ * C-ABI library is a separate one and its level handle is opaque, so the first
+ * device batch builds a second index inside that handle (another 0.7-1 ms for
+ * 2 000 tables, once) and the level's host footprint doubles from then on; a
+ * level whose batches all stay below the threshold never pays either.
+ *
+ * max_index_bytes: the budget of the index (0: 256 MiB).  A level of heavily
+ * overlapping tables needs O(T^2) list entries; when the index would exceed
+ * the budget status() is OUT_OF_RANGE, nothing was built, and the caller keeps
+ * using LevelMultiGetFilter(cache, tables, ...). */
+class LevelIndex {
+ public:
+  explicit LevelIndex(const vector<TableRange> &tables, uint64_t max_index_bytes = 0);
+  ~LevelIndex();
+  LevelIndex(const LevelIndex &) = delete;
+  LevelIndex &operator=(const LevelIndex &) = delete;
+  RC status() const { return status_; }
+  size_t tables() const { return tables_.size(); }
+  const vector<string_view> &oids() const { return oid_views_; }
+  uint32_t longest_list() const; /* no key has more candidates */
+  uint32_t mean_list() const;    /* the mean length of a region's list, rounded up */
+  /* LevelCandidates from the host copy: no decode, no sort, no sweep -- a
+   * binary search and a copy per key */
+  void Candidates(const vector<string_view> &user_keys, int64_t seq, vector<uint32_t> &begin,
+                  vector<uint32_t> &table) const;
+  /* The C-ABI level (adl_bloom_level_create from the same tables and budget),
+   * made by the first call: batches that stay on the host never need it.
+   * NULL when that failed (device_status()). */
+  adl_bloom_level *handle();
+  RC device_status() const { return device_status_; }
+
+ private:
+  unique_ptr<adl_level::Index> ix_; /* the host copy (level_index_core.hpp) */
+  vector<TableRange> tables_;       /* for handle() */
+  vector<string_view> oid_views_;
+  uint64_t max_index_bytes_;
+  std::once_flag handle_once_;
+  adl_bloom_level *h_ = nullptr;
+  RC device_status_ = OK;
+  RC status_;
+};
+
+/* LevelMultiGetFilter over a resident index: the same begin / table / maybe /
+ * uncached as the call above on the tables the index was built from.  Batches
+ * of fewer than ADL_BLOOM_LEVEL_DEVICE_MIN_KEYS keys (0 = never
+ * the device) are looked up in the host copy and probed as above; larger ones
+ * upload their keys only, and selection, list expansion and the probes all run
+ * on the device (adl_bloom_level_multiget). */
+RC LevelMultiGetFilter(FilterCache &cache, LevelIndex &level, const vector<string_view> &user_keys, int64_t seq,
+                       MultiGetFilterResult &out);
 
 }  // namespace adl

@@ -1,0 +1,335 @@
+// adlsm-tree_amd/csrc/level_index_core.hpp -- the level index both libraries
+// share (host C++ only, header-only): the region sweep that used to run inside
+// every LevelCandidates call, done ONCE per level, and the host lookup in it.
+//
+// A table t is a candidate for the lookup mk = (u, seq, OP_PUT)
+// (src/revision.cpp:281-287) iff mn[t].user <= u and !(mx[t] < mk): u in
+// [mn.user, mx.user), plus u == mx.user unless mx[t] < (mx.user, seq, OP_PUT).
+// So the candidate list is constant on each region the tables' boundary user
+// keys B cut the key space into, except for that one seq-dependent case.  The
+// index keeps, per region, the table list in Level::Get's visiting order; in a
+// point region a table whose max user key is that boundary is listed with bit
+// 31 set, and a lookup at `seq` drops such an entry exactly when
+// mx_seq > seq || (mx_seq == seq && mx_op > 0).  Nothing else depends on seq,
+// so the index lives as long as the level's revision does.
+//
+// Region numbering: 2i = the gap before B[i], 2i+1 = B[i] itself, 2*NB = the
+// gap after the last boundary.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <numeric>
+#include <string>
+#include <string_view>
+#include <vector>
+
+namespace adl_level {
+
+constexpr uint32_t kGoneAtMaxFlag = 0x80000000u;  // entry bit 31: listed at its own max user key
+constexpr uint32_t kTableMask = 0x7fffffffu;
+constexpr uint64_t kDefaultIndexBytes = 256ull << 20;  // the budget of an index when the caller names none
+
+/* An inner key decoded as MemKey::FromKey does (src/keys.cpp:86-91); keys
+ * shorter than the 9-byte suffix compare as (whole key, seq 0, op 0). */
+struct Decoded {
+  std::string_view user;
+  int64_t seq = 0;
+  int op = 0;
+};
+
+inline Decoded Decode(std::string_view k) {
+  Decoded d;
+  if (k.size() < 9) {
+    d.user = k;
+    return d;
+  }
+  d.user = k.substr(0, k.size() - 9);
+  memcpy(&d.seq, k.data() + k.size() - 9, 8);
+  d.op = (unsigned char)k[k.size() - 1];
+  return d;
+}
+
+/* MemKey::operator< (src/keys.cpp:61-74) */
+inline bool Less(const Decoded &a, const Decoded &b) {
+  const int cmp = a.user.compare(b.user);
+  if (cmp < 0) return true;
+  if (cmp == 0) {
+    if (a.seq > b.seq) return true;
+    if (a.seq == b.seq && a.op > b.op) return true;
+  }
+  return false;
+}
+
+/* the first 16 bytes of a user key, zero padded, as two big-endian words: two
+ * u64 compares order most keys; a tie ("ab" and "ab\0" tie) says nothing */
+struct Pref {
+  uint64_t hi, lo;
+};
+
+/* the first n <= 8 bytes at p as a little-endian word, zero padded.  Loads
+ * that overlap instead of a copy into a stack word: reading that word back
+ * right after byte-wise stores stalls until the stores retire, which serialises
+ * a batch's look-ups. */
+inline uint64_t LoadUpTo8(const char *p, size_t n) {
+  if (n >= 8) {
+    uint64_t v;
+    memcpy(&v, p, 8);
+    return v;
+  }
+  if (n >= 4) {
+    uint32_t a, b;
+    memcpy(&a, p, 4);
+    memcpy(&b, p + n - 4, 4);
+    return a | (uint64_t)b << (8 * (n - 4));
+  }
+  if (n == 0) return 0;
+  return (uint64_t)(uint8_t)p[0] | (uint64_t)(uint8_t)p[n / 2] << (8 * (n / 2)) |
+         (uint64_t)(uint8_t)p[n - 1] << (8 * (n - 1));
+}
+
+inline Pref PrefixOf(std::string_view u) {
+  const char *p = u.data();
+  const size_t n = u.size();
+  uint64_t hi, lo = 0;
+  if (n >= 16) {
+    memcpy(&hi, p, 8);
+    memcpy(&lo, p + 8, 8);
+  } else if (n > 8) {
+    memcpy(&hi, p, 8);
+    memcpy(&lo, p + n - 8, 8);  // bytes n-8 .. n-1: drop the ones below byte 8
+    lo >>= 8 * (16 - n);
+  } else {
+    hi = LoadUpTo8(p, n);
+  }
+  return Pref{__builtin_bswap64(hi), __builtin_bswap64(lo)};
+}
+
+struct Index {
+  uint32_t num_tables = 0;
+  uint32_t num_boundaries = 0;     // NB
+  std::string bbytes;              // the sorted distinct boundary user keys, back to back
+  std::vector<uint32_t> boff;      // NB + 1 offsets into bbytes
+  std::vector<Pref> pref;          // NB prefixes
+  std::vector<uint32_t> rbeg;      // 2 NB + 2: region r's list = rlist[rbeg[r], rbeg[r+1])
+  std::vector<uint32_t> rlist;     // table | kGoneAtMaxFlag, in visiting order
+  std::vector<int64_t> mx_seq;     // per table: its max inner key's seq
+  std::vector<uint8_t> mx_op;      // and op
+  uint32_t longest = 0;            // the longest region list
+
+  std::string_view boundary(size_t i) const { return std::string_view(bbytes.data() + boff[i], boff[i + 1] - boff[i]); }
+  /* the bytes the device copy takes (and close to what this one does) */
+  uint64_t bytes() const {
+    return 16ull * num_boundaries + bbytes.size() + 4ull * boff.size() + 4ull * rbeg.size() + 4ull * rlist.size() +
+           9ull * num_tables;
+  }
+  bool gone(uint32_t entry, int64_t seq) const {
+    if (!(entry & kGoneAtMaxFlag)) return false;
+    const uint32_t t = entry & kTableMask;
+    return mx_seq[t] > seq || (mx_seq[t] == seq && mx_op[t] > 0);
+  }
+  /* boundary i < u, p = PrefixOf(u).  The prefixes compare as one 128-bit
+   * number, without a branch; only a tie (rare: the first 16 bytes equal) reads
+   * the boundary's bytes. */
+  bool less_than(size_t i, const Pref &p, std::string_view u) const {
+    const unsigned __int128 b = (unsigned __int128)pref[i].hi << 64 | pref[i].lo;
+    const unsigned __int128 k = (unsigned __int128)p.hi << 64 | p.lo;
+    if (__builtin_expect(b == k, 0)) return boundary(i) < u;
+    return b < k;
+  }
+  /* lower_bound of u among the boundaries.  kBranchFree: the step is
+   * arithmetic, not a branch.  Which half holds a key is a coin toss per step,
+   * and a large batch's look-ups spend most of a branching search on
+   * mispredicted branches; a small batch that a caller repeats is the other
+   * way round (the predictor learns it, and the arithmetic form is one
+   * dependent chain per key), see kBranchFreeMinKeys. */
+  template <bool kBranchFree>
+  uint32_t lower_bound(std::string_view u, const Pref &p) const {
+    size_t lo = 0, n = num_boundaries;
+    if constexpr (kBranchFree) {
+      if (!n) return 0;
+      while (n > 1) {
+        const size_t h = n / 2;
+        lo += (size_t)less_than(lo + h - 1, p, u) * h;
+        n -= h;
+      }
+      return (uint32_t)(lo + less_than(lo, p, u));
+    } else {
+      while (n) {
+        const size_t h = n / 2;
+        if (less_than(lo + h, p, u)) {
+          lo += h + 1;
+          n -= h + 1;
+        } else {
+          n = h;
+        }
+      }
+      return (uint32_t)lo;
+    }
+  }
+  uint32_t lower_bound(std::string_view u) const { return lower_bound<true>(u, PrefixOf(u)); }
+  template <bool kBranchFree = true>
+  uint32_t region(std::string_view u) const {
+    const Pref p = PrefixOf(u);
+    const uint32_t j = lower_bound<kBranchFree>(u, p);
+    if (j == num_boundaries || pref[j].hi != p.hi || pref[j].lo != p.lo) return 2 * j;
+    return boundary(j) == u ? 2 * j + 1 : 2 * j;
+  }
+};
+
+/* The batch size from which a look-up searches without branches, measured on
+ * the MI355X host with each batch repeated ("Resident
+ * level index", the table of the two searches; profiles/level_index/
+ * search_ab.jsonl): on 16-table levels the branching search is 4-24 us faster
+ * from 1 000 to 4 000 keys, at 8 000 keys it wins by 31 us with one candidate
+ * per key and loses by 27 us with 3.2, and at 65 536 the branch-free one is
+ * 23-31 % faster. */
+constexpr size_t kBranchFreeMinKeys = 8192;
+
+/* Lookup (below) with the search chosen at compile time. */
+template <bool kBranchFree, class KeyAt>
+inline void LookupImpl(const Index &ix, size_t K, KeyAt &&key_at, int64_t seq, uint32_t *begin,
+                       std::vector<uint32_t> &table) {
+  std::vector<uint32_t> reg(K);
+  const uint32_t *const rbeg = ix.rbeg.data(), *const rlist = ix.rlist.data();
+  uint32_t total = 0;
+  begin[0] = 0;
+  for (size_t i = 0; i < K; ++i) {
+    const uint32_t r = ix.template region<kBranchFree>(key_at(i));
+    uint32_t n = rbeg[r + 1] - rbeg[r];
+    if (r & 1)  // only a point region lists tables at their own max user key
+      for (uint32_t p = rbeg[r]; p < rbeg[r + 1]; ++p) n -= ix.gone(rlist[p], seq);
+    reg[i] = r;
+    begin[i + 1] = total += n;
+  }
+  table.resize(total);
+  uint32_t *dst = table.data();
+  for (size_t i = 0; i < K; ++i) {
+    const uint32_t r = reg[i];
+    const uint32_t *src = rlist + rbeg[r], *const end = rlist + rbeg[r + 1];
+    if (!(r & 1)) {
+      dst = std::copy(src, end, dst);
+    } else {
+      for (; src != end; ++src)
+        if (!ix.gone(*src, seq)) *dst++ = *src & kTableMask;
+    }
+  }
+}
+
+/* The candidates of K keys at `seq`: key i's are table[begin[i] .. begin[i+1])
+ * (begin: K + 1 entries).  Two passes, as LevelCandidates always made them:
+ * every key's region and count, then the lists copied out into a table sized
+ * once.  key_at(i): key i as a string_view. */
+template <class KeyAt>
+inline void Lookup(const Index &ix, size_t K, KeyAt &&key_at, int64_t seq, uint32_t *begin,
+                   std::vector<uint32_t> &table) {
+  if (K >= kBranchFreeMinKeys) LookupImpl<true>(ix, K, key_at, seq, begin, table);
+  else LookupImpl<false>(ix, K, key_at, seq, begin, table);
+}
+
+/* Builds `ix` from the tables' (min, max) inner keys.  False, with nothing
+ * large allocated: the index would take more than max_bytes bytes (heavily
+ * overlapping tables need O(T^2) list entries), or is beyond the u32 / 2^24
+ * limits of the layout. */
+inline bool Build(const std::string_view *mins, const std::string_view *maxs, size_t T, uint64_t max_bytes, Index &ix) {
+  ix = Index{};
+  if (T >= kTableMask) return false;
+  ix.num_tables = (uint32_t)T;
+  // files_meta_ order (ascending min_inner_key, stable), visited in reverse
+  std::vector<Decoded> mn(T), mx(T);
+  for (size_t t = 0; t < T; ++t) {
+    mn[t] = Decode(mins[t]);
+    mx[t] = Decode(maxs[t]);
+  }
+  std::vector<uint32_t> asc(T);
+  std::iota(asc.begin(), asc.end(), 0u);
+  std::stable_sort(asc.begin(), asc.end(), [&](uint32_t a, uint32_t b) { return Less(mn[a], mn[b]); });
+  std::vector<std::string_view> B;
+  B.reserve(2 * T);
+  for (size_t t = 0; t < T; ++t) {
+    B.push_back(mn[t].user);
+    B.push_back(mx[t].user);
+  }
+  std::sort(B.begin(), B.end());
+  B.erase(std::unique(B.begin(), B.end()), B.end());
+  const size_t NB = B.size();
+  ix.num_boundaries = (uint32_t)NB;
+  uint64_t bbytes = 0;
+  for (std::string_view b : B) bbytes += b.size();
+  if (bbytes > 0xffffffffull) return false;
+  ix.bbytes.reserve(bbytes);
+  ix.boff.assign(1, 0);
+  ix.boff.reserve(NB + 1);
+  ix.pref.reserve(NB);
+  for (std::string_view b : B) {
+    ix.bbytes.append(b.data(), b.size());
+    ix.boff.push_back((uint32_t)ix.bbytes.size());
+    ix.pref.push_back(PrefixOf(b));
+  }
+  ix.mx_seq.resize(T);
+  ix.mx_op.resize(T);
+  for (size_t t = 0; t < T; ++t) {
+    ix.mx_seq[t] = mx[t].seq;
+    ix.mx_op[t] = (uint8_t)mx[t].op;
+  }
+  // per boundary: the tables that enter at it (ascending min order) and leave
+  // at it.  A table whose max user key sorts before its min (no real table) is
+  // never a candidate.
+  std::vector<std::vector<uint32_t>> ins(NB), outs(NB);
+  for (uint32_t t : asc)
+    if (!(mx[t].user < mn[t].user)) ins[ix.lower_bound(mn[t].user)].push_back(t);
+  for (size_t t = 0; t < T; ++t)
+    if (!(mx[t].user < mn[t].user)) outs[ix.lower_bound(mx[t].user)].push_back((uint32_t)t);
+  // the size of the lists before any of them is built
+  uint64_t total = 0, longest = 0;
+  {
+    uint64_t active = 0;
+    for (size_t i = 0; i < NB; ++i) {
+      total += active;  // the gap before B[i]
+      active += ins[i].size();
+      total += active;  // B[i]: the tables that end here are still listed (flagged)
+      longest = std::max(longest, active);
+      active -= outs[i].size();
+    }
+    total += active;  // (0: every table has left)
+  }
+  ix.rbeg.assign(2 * NB + 2, 0);
+  if (total > 0xffffffffull) return false;
+  if (longest >= (1u << 24)) return false;  // 256 lists of a workgroup's keys add up in a u32
+  ix.longest = (uint32_t)longest;
+  if (16ull * NB + bbytes + 4ull * (NB + 1) + 4ull * (2 * NB + 2) + 4ull * total + 9ull * T > max_bytes)
+    return false;
+  // One sweep builds every region's list in visiting order: a table enters at
+  // the front of the active list (ascending min order, so the list stays in
+  // visiting order) and leaves after its max.
+  ix.rlist.reserve(total);
+  constexpr uint32_t kNil = ~0u;
+  std::vector<uint32_t> nxt(T, kNil), prv(T, kNil);
+  std::vector<uint8_t> ends_here(T, 0);
+  uint32_t head = kNil;
+  auto record = [&](size_t r) {
+    for (uint32_t t = head; t != kNil; t = nxt[t]) ix.rlist.push_back(ends_here[t] ? t | kGoneAtMaxFlag : t);
+    ix.rbeg[r + 1] = (uint32_t)ix.rlist.size();
+  };
+  for (size_t i = 0; i < NB; ++i) {
+    record(2 * i);
+    for (uint32_t t : ins[i]) {
+      nxt[t] = head;
+      prv[t] = kNil;
+      if (head != kNil) prv[head] = t;
+      head = t;
+    }
+    for (uint32_t t : outs[i]) ends_here[t] = 1;
+    record(2 * i + 1);
+    for (uint32_t t : outs[i]) {
+      if (prv[t] != kNil) nxt[prv[t]] = nxt[t];
+      else head = nxt[t];
+      if (nxt[t] != kNil) prv[nxt[t]] = prv[t];
+    }
+  }
+  record(2 * NB);
+  return true;
+}
+
+}  // namespace adl_level

@@ -342,6 +342,78 @@ int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *cache, const cha
                                         const uint32_t *h_pair_table, uint8_t *h_out, uint64_t *h_uncached,
                                         void *stream);
 
+/* ------------------------------------------- resident level index */
+
+/* A level described once -- where a revision installs it -- and asked about
+ * many times: which of its tables Level::Get visits for a lookup key
+ * (src/revision.cpp:278-287: files_meta_ ordered by min_inner_key, walked in
+ * reverse, a table skipped when its [min_inner_key, max_inner_key] range does
+ * not cover MemKey(user_key, seq, OP_PUT)).  The tables' boundary user keys
+ * cut the key space into regions (a gap between two of them, or one of them);
+ * the index holds the sorted boundaries and every region's candidate tables in
+ * visiting order.  It does not depend on a lookup's seq: a table listed at its
+ * own max user key carries its max (seq, op), and a lookup drops it when
+ * max_seq > seq || (max_seq == seq && max_op > 0).  Immutable once created;
+ * any number of threads may use one level at once.  The device copy is made
+ * by the first device call on it (that one call waits for the upload on a
+ * stream of the calling thread's; create and stats need no GPU). */
+typedef struct adl_bloom_level adl_bloom_level;
+
+/* Table t (an index < num_tables, the value the calls below report): its key
+ * range as inner keys (user key + LE64 seq + op byte; a key shorter than 9
+ * bytes is a user key with seq 0, op 0) and the oid its filter block is cached
+ * under.  oids may be NULL (no adl_bloom_level_multiget then).  A table whose
+ * max user key sorts before its min is never a candidate.  max_index_bytes:
+ * the budget of the index, 0 = 256 MiB; heavily overlapping tables need
+ * O(num_tables^2) list entries, and ADL_ERR_TOO_LARGE says the index would
+ * exceed the budget (nothing is built: select on the host per batch instead),
+ * or that a single key could have 2^24 candidates or more. */
+int adl_bloom_level_create(const char *const *oids, const uint64_t *oid_lens, const char *const *min_inner_keys,
+                           const uint64_t *min_lens, const char *const *max_inner_keys, const uint64_t *max_lens,
+                           uint32_t num_tables, uint64_t max_index_bytes, adl_bloom_level **level);
+/* No call on the level may be running or start once this is called. */
+int adl_bloom_level_destroy(adl_bloom_level *level);
+
+/* regions, entries of all region lists, the bytes of the device copy and the
+ * longest list (each optional): no key has more candidates than
+ * *longest_list, so num_keys * *longest_list pairs always suffice. */
+int adl_bloom_level_stats(const adl_bloom_level *level, uint32_t *regions, uint64_t *list_entries,
+                          uint64_t *device_bytes, uint32_t *longest_list);
+
+/* Selection on the device: key i's candidate tables are d_pair_table
+ * [d_pair_begin[i] .. d_pair_begin[i+1]) in visiting order.  Stream-ordered on
+ * `stream` with no synchronisation (but see the first call, above):
+ * d_pair_begin (num_keys+1
+ * u32) and d_pair_table are the arrays adl_bloom_probe_fanout_device
+ * consumes.  d_pair_begin is always complete and *d_num_pairs (a device u64)
+ * the total needed; entries from pair_capacity on are not written.  A total
+ * of 2^32 or more leaves d_pair_begin meaningless.  d_keys as for the probes:
+ * any alignment, no byte outside a key is read.  d_workspace: 256-byte
+ * aligned, adl_bloom_level_candidates_workspace_bytes(num_keys) bytes. */
+uint64_t adl_bloom_level_candidates_workspace_bytes(uint64_t num_keys);
+int adl_bloom_level_candidates_device(adl_bloom_level *level, const uint8_t *d_keys, const uint64_t *d_offsets,
+                                      uint64_t num_keys, uint32_t key_stride, int64_t seq, uint32_t *d_pair_begin,
+                                      uint32_t *d_pair_table, uint64_t pair_capacity, uint64_t *d_num_pairs,
+                                      void *d_workspace, uint64_t workspace_bytes, void *stream);
+
+/* Level multi-get: uploads the keys (and offsets) only; selection, list
+ * expansion and the probes run on the device; h_pair_begin (num_keys+1),
+ * h_pair_table and h_out (one byte per pair) come back.  The level's oids are
+ * resolved and pinned in `cache` as adl_bloom_filter_cache_probe_fanout does
+ * with its oid list, and the answers are that call's on the same lists: a
+ * table that is not cached answers 1 and is counted in *h_uncached, a filter
+ * the block does not have answers 0, each table is probed with the k of its
+ * own block.  *num_pairs is the total; when it exceeds pair_capacity the call
+ * returns ADL_ERR_WORKSPACE with h_pair_begin complete and nothing else
+ * written, and ADL_ERR_TOO_LARGE when it is 2^32 or more.  Synchronous.
+ * Replaces Level::Get's loop over the level's tables (src/revision.cpp:265-310)
+ * and SSTableReader::Get's filter check for a batch of lookup keys. */
+int adl_bloom_level_multiget(adl_bloom_level *level, adl_bloom_filter_cache *cache, uint32_t filter,
+                             const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t num_keys,
+                             uint32_t key_stride, int64_t seq, uint32_t *h_pair_begin, uint32_t *h_pair_table,
+                             uint8_t *h_out, uint64_t pair_capacity, uint64_t *num_pairs, uint64_t *h_uncached,
+                             void *stream);
+
 /* ------------------------------------------- write-through builds into the cache */
 
 /* A table's filter block built straight into a reserved range of the cache
