@@ -16,6 +16,15 @@
 //     LevelMultiGetFilter(cache, tables, ...) on the same input: begin,
 //     table, maybe and uncached.  Exit 0 = all equal.
 //
+//   level_index_test --race
+//     Eight threads share ONE freshly made LevelIndex (the 12 overlapping
+//     tables) and are released together; the first call of each is a 3 000-key
+//     batch on the device path, so handle()'s call_once and the upload of the
+//     device copy race.  Each thread then alternates 3 000-key and 300-key
+//     batches at its own sequence numbers, and every MultiGetFilterResult must
+//     equal the one LevelMultiGetFilter(cache, tables, ...) gave on one thread
+//     beforehand.  Exit 0 = all equal.
+//
 //   level_index_test --bench <tables> <stride> <span> <keys>
 //     level_fanout_test --bench's level and batch, timed three ways in one
 //     process, one after the other: LevelMultiGetFilter(cache, index, ...),
@@ -33,9 +42,11 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "filter_block.hpp"
@@ -201,6 +212,73 @@ int Check() {
   return failures || pairs == 0 || hits == 0 || hits == pairs ? 1 : 0;
 }
 
+// Eight threads whose first call on a shared, never used LevelIndex is the
+// device path.
+int Race() {
+  setenv("ADL_BLOOM_LEVEL_DEVICE_MIN_KEYS", "1000", 0);
+  constexpr int kThreads = 8, kRounds = 6;
+  FilterCache cache(64ull << 20, 4096);
+  if (cache.status()) return 1;
+  static const int kBpk[3] = {10, 3, 16};
+  TestLevel overlap;
+  if (!MakeLevel(cache, 12, 500, 2000, kBpk, 3, "ovl", 5, overlap)) return 1;
+  // the batches and what they have to give, made on this thread without an index
+  const size_t kKeys[2] = {3000, 300};
+  const int64_t kSeqs[4] = {INT64_MAX, 1999, 2499, 100};
+  std::vector<std::string> q[2];
+  std::vector<std::string_view> qv[2];
+  MultiGetFilterResult want[2][4];
+  size_t pairs = 0, hits = 0;
+  for (int b = 0; b < 2; ++b) {
+    uint64_t s = 0xACE + kKeys[b];
+    for (size_t i = 0; i < kKeys[b]; ++i) {
+      s = s * 6364136223846793005ull + 1442695040888963407ull;
+      const uint64_t r = s >> 17;
+      std::string k = UserKey(r % (overlap.key_space + 100));
+      if (i % 3 == 2) k.back() = '#';
+      else if (i % 7 == 6) {
+        const TableRange &t = overlap.tables[r % overlap.tables.size()];
+        k = t.max_inner_key.substr(0, t.max_inner_key.size() - 9);
+      }
+      q[b].push_back(std::move(k));
+    }
+    qv[b].assign(q[b].begin(), q[b].end());
+    for (int j = 0; j < 4; ++j) {
+      if (LevelMultiGetFilter(cache, overlap.tables, qv[b], kSeqs[j], want[b][j]) != OK) return 1;
+      pairs += want[b][j].table.size();
+      for (uint8_t m : want[b][j].maybe) hits += m;
+    }
+  }
+  LevelIndex index(overlap.tables);  // no call on it before the threads start
+  if (index.status()) return 1;
+  std::atomic<int> ready{0}, bad{0};
+  std::atomic<bool> go{false};
+  std::vector<std::thread> th;
+  for (int t = 0; t < kThreads; ++t)
+    th.emplace_back([&, t] {
+      ++ready;
+      while (!go.load(std::memory_order_acquire)) std::this_thread::yield();
+      for (int r = 0; r < kRounds; ++r) {
+        const int b = r & 1, j = (t + r) & 3;  // round 0: 3 000 keys, the device path
+        MultiGetFilterResult got;
+        const RC rc = LevelMultiGetFilter(cache, index, qv[b], kSeqs[j], got);
+        const MultiGetFilterResult &w = want[b][j];
+        if (rc != OK || got.begin != w.begin || got.table != w.table || got.maybe != w.maybe ||
+            got.uncached != w.uncached) {
+          ++bad;
+          fprintf(stderr, "MISMATCH thread %d round %d K=%zu seq=%lld: rc %d, pairs %zu / %zu\n", t, r, kKeys[b],
+                  (long long)kSeqs[j], (int)rc, got.table.size(), w.table.size());
+        }
+      }
+    });
+  while (ready.load() < kThreads) std::this_thread::yield();
+  go.store(true, std::memory_order_release);
+  for (std::thread &x : th) x.join();
+  printf("%d threads, %d calls each, %zu pairs, %zu maybe, %d mismatches\n", kThreads, kRounds, pairs, hits,
+         bad.load());
+  return bad.load() || pairs == 0 || hits == 0 || hits == pairs ? 1 : 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -209,8 +287,10 @@ int main(int argc, char **argv) {
                  (size_t)strtoull(argv[5], nullptr, 10), false);
   if (argc == 3 && std::string(argv[1]) == "--bench-readpath")
     return Bench(16, 50000, 200000, (size_t)strtoull(argv[2], nullptr, 10), true);
+  if (argc == 2 && std::string(argv[1]) == "--race") return Race();
   if (argc != 1) {
-    fprintf(stderr, "usage: level_index_test | --bench <tables> <stride> <span> <keys> | --bench-readpath <keys>\n");
+    fprintf(stderr,
+            "usage: level_index_test | --race | --bench <tables> <stride> <span> <keys> | --bench-readpath <keys>\n");
     return 2;
   }
   return Check();

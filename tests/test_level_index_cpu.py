@@ -7,10 +7,11 @@ Host code only: no compute call reaches the GPU (the device copy of an index
 is made by its first device call)."""
 import ctypes
 import os
-import struct
 
 import numpy as np
 import pytest
+
+from levelkeys import P40, inner, max_tail, special_users
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "adlsm-tree_amd", "lib", "libadlfilterblock.so")
@@ -32,10 +33,6 @@ def mirror():
                   ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                   ctypes.c_uint64]
     return f, g
-
-
-def inner(user: bytes, seq: int, op: int) -> bytes:
-    return user + struct.pack("<q", seq) + bytes([op])
 
 
 def _arr(bs):
@@ -177,3 +174,130 @@ def test_over_budget_in_the_mirror(mirror):
     args = (ks, kl.ctypes.data, kb.ctypes.data, 1, seqs.ctypes.data, begin.ctypes.data, table.ctypes.data, 65)
     assert g(mins, ml.ctypes.data, maxs, xl.ctypes.data, 64, 4096, *args) == -2
     assert g(mins, ml.ctypes.data, maxs, xl.ctypes.data, 64, 0, *args) == 2  # tables 0 and 1 cover u00001
+
+
+# ------------------------------------------------------------------ batches on both sides of kBranchFreeMinKeys
+BIG_SEQS = (24, 25, 26, 0, 2**63 - 1)
+BIG_KS = (8191, 8192, 20000)  # kBranchFreeMinKeys = 8192: the branching search below it, the branch-free one from it
+
+
+def _special_level(n):
+    """n tables over the first boundaries of special_users() (all of them when
+    n is None): random ranges, max (seq, op) cycling through max_tail, one
+    table given as bare user keys, one with max < min."""
+    sp = special_users()
+    if n == 0:
+        return []
+    if n == 1:
+        return [(inner(P40[:16], 3, 0), inner(P40[:16], 25, 1))]  # min user == max user: a single boundary
+    rng = np.random.default_rng(16)
+    tabs = []
+    for i in range(16):
+        a, b = sorted(int(x) for x in rng.integers(0, len(sp), 2))
+        tabs.append((inner(sp[a], int(rng.integers(0, 50)), int(rng.integers(0, 2))), inner(sp[b], *max_tail(i))))
+    tabs[5] = (b"ab", b"\xfe\x80")
+    tabs[7] = (inner(sp[-1], 1, 0), inner(sp[0], 25, 0))
+    # (every boundary of special_users() used)
+    tabs += [(inner(sp[i], 9, 0), inner(sp[min(i + 1, len(sp) - 1)], *max_tail(i))) for i in range(0, len(sp), 2)]
+    return tabs
+
+
+def _big_pool():
+    sp = special_users()
+    keys = set(sp)
+    for u in sp:
+        keys |= {u + b"\0", u + b"\x80", u[:-1], u[:16] + b"\x01", u[:17] + b"\xee", u[:40] + b"\x05"}
+    for n in range(1, 18):  # LoadUpTo8 (1-8 bytes) and PrefixOf's overlapping load (9-15), 16 and 17
+        keys |= {P40[:n], b"q" * n, b"\x7f" * (n - 1) + b"\x80", b"\xff" * n}
+    keys |= {P40[:24] + b"\x01", b"q" * 40, bytes(300), b"\xff" * 300, P40 + bytes(259) + b"\x01"}
+    return sorted(keys)
+
+
+def _check_big_pool(pool):
+    assert b"" in pool and b"ab" in pool and b"ab\0" in pool
+    assert {len(k) for k in pool} >= set(range(0, 18)) | {24, 40, 300}
+    assert any(k and k[0] >= 0x80 for k in pool) and any(len(k) > 16 and k[16] >= 0x80 for k in pool)
+    for n in (16, 17, 40):  # distinct keys that share n bytes and differ right after them
+        assert any(a != b and len(a) > n and len(b) > n and a[:n] == b[:n] and a[n] != b[n]
+                   for a in pool for b in pool if a[:n] == P40[:n]), n
+    sp = special_users()
+    assert set(sp) <= set(pool)
+    assert sorted(sp, key=lambda k: [b - 256 if b >= 128 else b for b in k]) != sp
+
+
+def _raw_index_candidates(g, tables, batches):
+    """adl_level_index_candidates -> per batch (begin u32[K+1], table u32[pairs])."""
+    mins, ml = _arr([t[0] for t in tables])
+    maxs, xl = _arr([t[1] for t in tables])
+    allkeys = [k for keys, _ in batches for k in keys]
+    ks, kl = _arr(allkeys)
+    kb = np.concatenate([[0], np.cumsum([len(keys) for keys, _ in batches])]).astype(np.uint32)
+    seqs = np.array([s for _, s in batches], dtype=np.int64)
+    cap = max(len(tables), 1) * len(allkeys) + 1
+    begin = np.full(len(allkeys) + len(batches), 0xA5A5A5A5, dtype=np.uint32)
+    table = np.full(cap, 0xA5A5A5A5, dtype=np.uint32)
+    n = g(mins, ml.ctypes.data, maxs, xl.ctypes.data, len(tables), 0, ks, kl.ctypes.data, kb.ctypes.data,
+          len(batches), seqs.ctypes.data, begin.ctypes.data, table.ctypes.data, cap)
+    assert n >= 0, n
+    out, base = [], 0
+    for b in range(len(batches)):
+        bg = begin[int(kb[b]) + b:int(kb[b + 1]) + b + 1]
+        out.append((bg, table[base:base + int(bg[-1])]))
+        base += int(bg[-1])
+    assert base == n and (table[n:] == 0xA5A5A5A5).all()
+    return out
+
+
+def _raw_fresh(f, tables, keys, seq):
+    mins, ml = _arr([t[0] for t in tables])
+    maxs, xl = _arr([t[1] for t in tables])
+    ks, kl = _arr(keys)
+    cap = max(len(tables), 1) * len(keys) + 1
+    begin = np.zeros(len(keys) + 1, dtype=np.uint32)
+    table = np.zeros(cap, dtype=np.uint32)
+    n = f(mins, ml.ctypes.data, maxs, xl.ctypes.data, len(tables), ks, kl.ctypes.data, len(keys), seq,
+          begin.ctypes.data, table.ctypes.data, cap)
+    assert n >= 0
+    return begin, table[:n]
+
+
+@pytest.mark.parametrize("tables_n", [None, 0, 1], ids=["special", "no_boundary", "one_boundary"])
+def test_batches_on_both_sides_of_the_branch_free_threshold(mirror, oracle, tables_n):
+    """8 191 keys (LookupImpl<false>), 8 192 and 20 000 (LookupImpl<true>) drawn
+    from a pool around special_users(), at five sequence numbers: the index's
+    answer and the per-call selection's both equal the oracle's lists of the
+    pool keys, entry for entry."""
+    f, g = mirror
+    tables = _special_level(tables_n)
+    pool = _big_pool()
+    _check_big_pool(pool)
+    users = {t[0][:-9] if len(t[0]) >= 9 else t[0] for t in tables} | {t[1][:-9] if len(t[1]) >= 9 else t[1]
+                                                                        for t in tables}
+    assert len(users) == {None: len(special_users()), 0: 0, 1: 1}[tables_n]
+    want = {seq: [oracle.level_candidates(tables, k, seq) for k in pool] for seq in BIG_SEQS}
+    if tables_n is None:
+        assert any(want[24][i] != want[26][i] for i in range(len(pool)))
+        assert any(want[0][i] != want[2**63 - 1][i] for i in range(len(pool)))
+        assert any(not x for x in want[25]) and max(len(x) for x in want[25]) >= 5
+    elif tables_n == 1:
+        assert want[26][pool.index(P40[:16])] == [0] and want[24][pool.index(P40[:16])] == []
+        assert sum(len(x) for x in want[26]) == 1
+    else:
+        assert not any(want[25])
+    rng = np.random.default_rng(8192)
+    batches, sels = [], []
+    for K in BIG_KS:
+        for seq in BIG_SEQS:
+            sel = rng.integers(0, len(pool), K)
+            sel[:len(pool)] = rng.permutation(len(pool))
+            sels.append(sel)
+            batches.append(([pool[int(i)] for i in sel], seq))
+    got = _raw_index_candidates(g, tables, batches)
+    for (keys, seq), sel, (bg, tb) in zip(batches, sels, got):
+        lens = np.array([len(x) for x in want[seq]], np.int64)
+        begin = np.concatenate([[0], np.cumsum(lens[sel])]).astype(np.uint32)
+        flat = np.array([t for i in sel for t in want[seq][int(i)]], np.uint32)
+        assert np.array_equal(bg, begin), (len(keys), seq, int(np.flatnonzero(bg != begin)[0]))
+        assert np.array_equal(tb, flat), (len(keys), seq, int(np.flatnonzero(tb != flat)[0]))
+        fb, ft = _raw_fresh(f, tables, keys, seq)
+        assert np.array_equal(fb, begin) and np.array_equal(ft, flat), (len(keys), seq)
