@@ -54,6 +54,10 @@ EXPORTS = (
     "adl_bloom_level_create", "adl_bloom_level_destroy", "adl_bloom_level_stats",
     "adl_bloom_level_candidates_workspace_bytes",
     "adl_bloom_level_candidates_device", "adl_bloom_level_multiget",
+    "adl_bloom_revision_create", "adl_bloom_revision_destroy", "adl_bloom_revision_stats",
+    "adl_bloom_revision_candidates_workspace_bytes", "adl_bloom_revision_candidates_device",
+    "adl_bloom_probe_fanout_hits_workspace_bytes", "adl_bloom_probe_fanout_hits_device",
+    "adl_bloom_revision_multiget",
 )
 
 _LIB = None
@@ -122,6 +126,18 @@ def lib() -> ctypes.CDLL:
                                                               vp, u64, vp]),
         "adl_bloom_level_multiget": (ctypes.c_int, [vp, vp, u32, vp, vp, u64, u32, ctypes.c_int64, vp, vp, vp, u64,
                                                      ctypes.POINTER(u64), ctypes.POINTER(u64), vp]),
+        "adl_bloom_revision_create": (ctypes.c_int, [vp, u32, ctypes.POINTER(vp)]),
+        "adl_bloom_revision_destroy": (ctypes.c_int, [vp]),
+        "adl_bloom_revision_stats": (ctypes.c_int, [vp, ctypes.POINTER(u32), vp, ctypes.POINTER(u32)]),
+        "adl_bloom_revision_candidates_workspace_bytes": (u64, [vp, u64]),
+        "adl_bloom_revision_candidates_device": (ctypes.c_int, [vp, vp, vp, u64, u32, ctypes.c_int64, vp, vp, u64, vp,
+                                                                 vp, u64, vp]),
+        "adl_bloom_probe_fanout_hits_workspace_bytes": (u64, [u64, u64]),
+        "adl_bloom_probe_fanout_hits_device": (ctypes.c_int, [vp, vp, u64, u32, vp, vp, u64, u32, vp, vp, vp, i32, vp,
+                                                               vp, u64, vp, vp, u64, vp]),
+        "adl_bloom_revision_multiget": (ctypes.c_int, [vp, vp, u32, vp, vp, u64, u32, ctypes.c_int64, vp, vp, u64,
+                                                        ctypes.POINTER(u64), u64, ctypes.POINTER(u64),
+                                                        ctypes.POINTER(u64), vp]),
         "adl_bloom_probe_device": (ctypes.c_int, [vp, vp, u64, u32, i32, vp, u64, vp, vp]),
         "adl_bloom_probe_batch_workspace_bytes": (u64, [u64, u32, i32, u32]),
         "adl_bloom_probe_batch_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, i32, vp, vp, u64, vp]),
@@ -443,6 +459,30 @@ def probe_fanout(keys, pair_begin, pair_filter, bitmaps, bitmap_off, offsets=Non
                                                bits_per_key, _dptr(out), _stream(stream)),
            "adl_bloom_probe_fanout_device")
     return out[:npairs]
+
+
+def probe_fanout_hits(keys, pair_begin, pair_filter, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10,
+                      hit_capacity: int | None = None, stream=None):
+    """probe_fanout's inputs; only the survivors come back: (hit_begin int32[n+1], hit_filter
+    int32[hit_capacity], num_hits int64[1]) device tensors read as unsigned -- key i's hits are
+    hit_filter[hit_begin[i]:hit_begin[i+1]], the filters of its pairs answered 1, in pair order.  Enqueued on
+    `stream` without a synchronise.  hit_capacity: default the number of pairs."""
+    torch = _torch()
+    pk, po, n, stride = _keyset(keys, offsets)
+    assert pair_begin.numel() == n + 1, "pair_begin: one entry per key and one more"
+    npairs = pair_filter.numel()
+    cap = npairs if hit_capacity is None else int(hit_capacity)
+    wsb = lib().adl_bloom_probe_fanout_hits_workspace_bytes(n, npairs)
+    with _on(stream):
+        hb = torch.empty(n + 1, dtype=torch.int32, device=keys.device)
+        hf = torch.empty(max(cap, 1), dtype=torch.int32, device=keys.device)
+        nh = torch.empty(1, dtype=torch.int64, device=keys.device)
+        ws = empty_device(wsb, keys.device)
+    _check(lib().adl_bloom_probe_fanout_hits_device(pk, po, n, stride, _dptr(pair_begin), _dptr(pair_filter), npairs,
+                                                    bitmap_off.numel() - 1, _dptr(bitmaps), _dptr(bitmap_off), None,
+                                                    bits_per_key, _dptr(hb), _dptr(hf), cap, _dptr(nh), _dptr(ws),
+                                                    wsb, _stream(stream)), "adl_bloom_probe_fanout_hits_device")
+    return hb, hf[:cap], nh
 
 
 def probe_batch(keys, filter_id, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10, stream=None,
@@ -872,6 +912,80 @@ class LevelIndex:
     def close(self):
         if self._h:
             lib().adl_bloom_level_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Revision:
+    """A revision (adl_bloom_revision): its levels' LevelIndex objects in Revision::Get's visiting order, level 0
+    first; None or a level of no tables is an empty level.  The levels are borrowed (this object keeps them
+    alive).  Every call reports GLOBAL table ids: table t of level l is stats()[1][l] + t."""
+
+    def __init__(self, levels):
+        self._h = ctypes.c_void_p()
+        self._levels = list(levels)
+        arr = (ctypes.c_void_p * max(len(self._levels), 1))(*[None if lv is None else lv._h.value
+                                                             for lv in self._levels])
+        _check(lib().adl_bloom_revision_create(ctypes.cast(arr, ctypes.c_void_p), len(self._levels),
+                                               ctypes.byref(self._h)), "adl_bloom_revision_create")
+
+    def stats(self):
+        """-> (levels, table_base uint32[levels + 1], the longest candidate list over all levels)."""
+        nl, lg = ctypes.c_uint32(), ctypes.c_uint32()
+        base = np.zeros(len(self._levels) + 1, dtype=np.uint32)
+        _check(lib().adl_bloom_revision_stats(self._h, ctypes.byref(nl), base.ctypes.data, ctypes.byref(lg)),
+               "adl_bloom_revision_stats")
+        return nl.value, base, lg.value
+
+    def candidates_device(self, keys, offsets=None, seq: int = 2**63 - 1, pair_capacity: int | None = None,
+                          stream=None):
+        """Selection over every level on the device from torch device tensors, enqueued on `stream` without a
+        synchronise: (pair_begin int32[n+1], pair_table int32[pair_capacity], num_pairs int64[1]) device
+        tensors, read as unsigned.  pair_capacity: default n * the longest list."""
+        torch = _torch()
+        pk, po, n, stride = _keyset(keys, offsets)
+        cap = n * self.stats()[2] if pair_capacity is None else int(pair_capacity)
+        wsb = lib().adl_bloom_revision_candidates_workspace_bytes(self._h, n)
+        with _on(stream):
+            pb = torch.empty(n + 1, dtype=torch.int32, device=keys.device)
+            pt = torch.empty(max(cap, 1), dtype=torch.int32, device=keys.device)
+            npairs = torch.empty(1, dtype=torch.int64, device=keys.device)
+            ws = empty_device(wsb, keys.device)
+        _check(lib().adl_bloom_revision_candidates_device(self._h, pk, po, n, stride, seq, _dptr(pb), _dptr(pt), cap,
+                                                          _dptr(npairs), _dptr(ws), wsb, _stream(stream)),
+               "adl_bloom_revision_candidates_device")
+        return pb, pt[:cap], npairs
+
+    def multiget_status(self, cache: "FilterCache", keys: np.ndarray, offsets=None, seq: int = 2**63 - 1,
+                        filter: int = 0, hit_capacity: int | None = None, pair_capacity: int = 0, stream=None):
+        """adl_bloom_revision_multiget: (status, hit_begin, hit_table, num_hits, num_pairs, uncached).
+        hit_capacity: default n * the longest list."""
+        keep, kp, po, n, stride = LevelIndex._host_keys(keys, offsets)
+        cap = n * self.stats()[2] if hit_capacity is None else int(hit_capacity)
+        hb = np.zeros(n + 1, dtype=np.uint32)
+        ht = np.zeros(max(cap, 1), dtype=np.uint32)
+        nh, npairs, unc = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        rc = lib().adl_bloom_revision_multiget(self._h, cache._h, filter, kp, po, n, stride, seq, hb.ctypes.data,
+                                               ht.ctypes.data, cap, ctypes.byref(nh), int(pair_capacity),
+                                               ctypes.byref(npairs), ctypes.byref(unc), _host_stream(stream))
+        return rc, hb, ht[:min(nh.value, cap)], nh.value, npairs.value, unc.value
+
+    def multiget(self, cache: "FilterCache", keys: np.ndarray, offsets=None, seq: int = 2**63 - 1, filter: int = 0,
+                 stream=None):
+        """Revision multi-get: keys up; selection over every level, probes and compaction on the device;
+        (hit_begin, hit_table, uncached) back -- per key the tables still to read, in visiting order."""
+        rc, hb, ht, _, _, unc = self.multiget_status(cache, keys, offsets, seq, filter, None, 0, stream)
+        _check(rc, "adl_bloom_revision_multiget")
+        return hb, ht, unc
+
+    def close(self):
+        if self._h:
+            lib().adl_bloom_revision_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):

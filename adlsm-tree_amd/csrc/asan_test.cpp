@@ -264,6 +264,30 @@ void LevelIndexChecks() {
   }
   CHECK(LevelIndex(wide, 4096).status() == OUT_OF_RANGE);
   CHECK(LevelIndex(wide).status() == OK && LevelIndex(wide).longest_list() == 64);
+  // A revision's host lookup: the levels' lists back to back as global ids; a
+  // missing and a table-less level are skipped; nine levels are refused.
+  std::vector<TableRange> one(1), none;
+  one[0].min_inner_key = inner("u120", 1, 0);
+  one[0].max_inner_key = inner("v101", 1, 0);
+  LevelIndex lw(wide), l1(one), l0(none);
+  RevisionIndex rev({&l1, nullptr, &l0, &lw, &l1});
+  CHECK(rev.status() == OK && rev.longest_list() == 66);
+  CHECK((rev.table_base() == std::vector<uint32_t>{0, 1, 1, 1, 65, 66}));
+  const std::vector<std::string> keys = {"u130", "", "v100", "zz"};
+  const std::vector<std::string_view> kv(keys.begin(), keys.end());
+  std::vector<uint32_t> b, t, bw, tw, b1, t1;
+  rev.Candidates(kv, INT64_MAX, b, t);
+  lw.Candidates(kv, INT64_MAX, bw, tw);
+  l1.Candidates(kv, INT64_MAX, b1, t1);
+  CHECK(b.size() == 5 && b[4] == t.size() && t.size() == tw.size() + 2 * t1.size());
+  for (size_t i = 0; i < kv.size(); ++i) {
+    std::vector<uint32_t> want(t1.begin() + b1[i], t1.begin() + b1[i + 1]);
+    for (uint32_t p = bw[i]; p < bw[i + 1]; ++p) want.push_back(1 + tw[p]);
+    for (uint32_t p = b1[i]; p < b1[i + 1]; ++p) want.push_back(65 + t1[p]);
+    CHECK(want == std::vector<uint32_t>(t.begin() + b[i], t.begin() + b[i + 1]));
+  }
+  CHECK(b[1] - b[0] == 33 && b[2] == b[1]);  // "u130": tables u100..u130 of `wide`, and `one` twice
+  CHECK(RevisionIndex(std::vector<LevelIndex *>(9, &l1)).status() == BAD_REVISION);
 }
 
 }  // namespace

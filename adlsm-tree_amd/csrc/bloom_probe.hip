@@ -19,6 +19,7 @@
 #include <new>
 
 #include "bloom_common.hpp"
+#include "level_index_impl.hpp"
 #include "probe_device.hpp"
 
 using namespace adl_dev;
@@ -136,6 +137,104 @@ __global__ __launch_bounds__(kBlockP) void bloom_probe_fanout_kernel(
       out[p] = hit;
     }
     __syncthreads();  // the next block of keys reuses sh1 / sh2 / spb
+  }
+}
+
+// The fan-out probe that also counts: the same 256 keys per workgroup, hashes
+// in LDS and lanes striding over the block's pairs, but the answer bytes go to
+// scratch (ans[p]) and what comes out is hits[i], the number of pairs of key i
+// answered 1 (counted in LDS), and one hit total per block of keys.  Every
+// answer is bloom_probe_fanout_kernel's.  (A kernel of its own, not a flag on
+// that one: the answer path of the level multi-get keeps its code and its
+// registers as measured.)
+template <class Keys>
+__global__ __launch_bounds__(kBlockP) void bloom_probe_fanout_count_kernel(
+    Keys keys, uint64_t nkeys, const uint32_t *__restrict__ pair_begin, const uint32_t *__restrict__ pair_filter,
+    uint32_t np, uint32_t k, const uint8_t *__restrict__ kf, uint32_t nf, const uint8_t *__restrict__ bitmaps,
+    const uint64_t *__restrict__ boff, const uint64_t *__restrict__ bend, uint8_t *__restrict__ ans,
+    uint32_t *__restrict__ hits, uint64_t *__restrict__ block_total) {
+  extern __shared__ ModLds lmod[];
+  __shared__ uint32_t sh1[kBlockP], sh2[kBlockP], spb[kBlockP + 1], shits[kBlockP];
+  __shared__ uint32_t scratch[kBlockP / kWave + 1];
+  const bool lds_tab = nf <= kLdsFilters;
+  if (lds_tab) mod_table_fill(lmod, nf, k, kf, boff, bend);  // (the first barrier below covers it)
+  const uint32_t t = threadIdx.x;
+  const uint64_t nblk = (nkeys + kBlockP - 1) / kBlockP;
+  for (uint64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const uint64_t kb = blk * kBlockP;
+    const uint32_t nk = (uint32_t)(nkeys - kb < (uint64_t)kBlockP ? nkeys - kb : (uint64_t)kBlockP);
+    shits[t] = 0;
+    if (t < nk) {
+      const uint32_t b = pair_begin[kb + t], e = pair_begin[kb + t + 1];
+      spb[t] = b;
+      if (t == nk - 1) spb[nk] = e;
+      if (e > b) {
+        uint32_t h1, h2;
+        keys.hash(kb + t, h1, h2);
+        sh1[t] = h1;
+        sh2[t] = h2;
+      }
+    }
+    __syncthreads();
+    const uint32_t p1 = spb[nk] < np ? spb[nk] : np;
+    for (uint64_t p = (uint64_t)spb[0] + t; p < p1; p += kBlockP) {
+      // the first j in [1, nk] with spb[j] > p (spb[nk] > p): key j - 1 owns p
+      uint32_t lo = 1, hi = nk;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (spb[mid] > (uint32_t)p) hi = mid; else lo = mid + 1;
+      }
+      uint8_t hit = 0;
+      uint64_t b0;
+      FastMod mod;
+      uint32_t kq;
+      if (filter_lookup(pair_filter[p], nf, lds_tab, lmod, k, kf, boff, bend, b0, mod, kq))
+        hit = probe_bits(bitmaps + b0, sh1[lo - 1], sh2[lo - 1], kq, mod);
+      ans[p] = hit;
+      if (hit) atomicAdd(&shits[lo - 1], 1u);  // (LDS, within the workgroup: a count, no order hangs on it)
+    }
+    __syncthreads();
+    const uint32_t mine = t < nk ? shits[t] : 0u;
+    if (t < nk) hits[kb + t] = mine;
+    uint32_t total;
+    (void)block_excl_scan<kBlockP>(mine, scratch, &total);  // (its barriers: sh1 / sh2 / spb / shits are free again)
+    if (t == 0) block_total[blk] = total;
+  }
+}
+
+// Workgroup b owns the pairs of keys [256 b, 256 b + 256): hit_begin of its
+// keys from their hit counts and the block's offset, then a stable stream
+// compaction of its pairs in rounds of 256 -- a lane per pair, the hit flags
+// scanned over the workgroup (block_excl_scan: wave scans, no atomic), so the
+// hits keep pair order.  Entries at hit_capacity and beyond are not written.
+__global__ __launch_bounds__(kBlockP) void fanout_compact_kernel(
+    uint64_t nkeys, const uint32_t *__restrict__ pair_begin, const uint32_t *__restrict__ pair_filter, uint32_t np,
+    const uint8_t *__restrict__ ans, const uint32_t *__restrict__ hits, const uint64_t *__restrict__ block_off,
+    uint32_t *__restrict__ hit_begin, uint32_t *__restrict__ hit_filter, uint64_t hit_capacity) {
+  __shared__ uint32_t scratch[kBlockP / kWave + 1];
+  const uint32_t t = threadIdx.x;
+  const uint64_t kb = blockIdx.x * (uint64_t)kBlockP;
+  const uint64_t i = kb + t;
+  const uint32_t nk = (uint32_t)(nkeys - kb < (uint64_t)kBlockP ? nkeys - kb : (uint64_t)kBlockP);
+  const uint32_t cnt = i < nkeys ? hits[i] : 0u;
+  uint32_t btotal;
+  const uint32_t excl = block_excl_scan<kBlockP>(cnt, scratch, &btotal);
+  const uint64_t base = block_off[blockIdx.x];
+  if (i < nkeys) {
+    hit_begin[i] = (uint32_t)(base + excl);
+    if (i == nkeys - 1) hit_begin[nkeys] = (uint32_t)(base + excl + cnt);
+  }
+  if (btotal == 0) return;  // (uniform)
+  const uint32_t pe = pair_begin[kb + nk];
+  const uint64_t p0 = pair_begin[kb], p1 = pe < np ? pe : np;
+  uint64_t w = base;
+  for (uint64_t r = p0; r < p1; r += kBlockP) {
+    const uint64_t p = r + t;
+    const bool hit = p < p1 && ans[p];
+    uint32_t rtotal;
+    const uint32_t at = block_excl_scan<kBlockP>(hit ? 1u : 0u, scratch, &rtotal);
+    if (hit && w + at < hit_capacity) hit_filter[w + at] = pair_filter[p];
+    w += rtotal;
   }
 }
 
@@ -317,7 +416,79 @@ int probe_fanout(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_
     return ADL_OK;
   });
 }
+uint64_t hits_ws_layout(uint64_t num_keys, uint64_t num_pairs, uint64_t &o_hits, uint64_t &o_btot, uint64_t &o_boff) {
+  const uint64_t nblk = (num_keys + kBlockP - 1) / kBlockP;
+  o_hits = adl_host::round_up(num_pairs, 256);  // after the answer bytes
+  o_btot = o_hits + adl_host::round_up(num_keys * 4, 256);
+  o_boff = o_btot + adl_host::round_up(nblk * 8, 256);
+  return o_boff + adl_host::round_up(nblk * 8, 256) + 256;
+}
 }  // namespace
+
+// Probe + hit count, the scan of the block totals, the compaction: three
+// launches whatever the batch holds.
+int adl_host::probe_fanout_hits_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys,
+                                       uint32_t key_stride, const uint32_t *d_pair_begin,
+                                       const uint32_t *d_pair_filter, uint64_t num_pairs, uint32_t num_filters,
+                                       const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end,
+                                       int32_t bits_per_key, const uint8_t *d_k, uint32_t *d_hit_begin,
+                                       uint32_t *d_hit_filter, uint64_t hit_capacity, uint64_t *d_num_hits,
+                                       void *d_workspace, uint64_t workspace_bytes, hipStream_t st) {
+  if (!d_hit_begin || !d_num_hits) return ADL_ERR_INVALID_ARG;
+  if (num_keys >= 0xffffffffull || num_pairs > 0xffffffffull) return ADL_ERR_TOO_LARGE;  // the begin arrays are u32
+  if (num_keys == 0 || num_pairs == 0) {
+    ADL_HIP_TRY(hipMemsetAsync(d_hit_begin, 0, (num_keys + 1) * 4, st));
+    ADL_HIP_TRY(hipMemsetAsync(d_num_hits, 0, 8, st));
+    return ADL_OK;
+  }
+  if (!d_keys || !d_pair_begin || !d_pair_filter || bits_per_key < 0 || !d_workspace) return ADL_ERR_INVALID_ARG;
+  if (hit_capacity && !d_hit_filter) return ADL_ERR_INVALID_ARG;
+  if (num_filters && (!d_bitmaps || !d_begin)) return ADL_ERR_INVALID_ARG;
+  if (!d_offsets && key_stride == 0) return ADL_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(d_workspace) % 256) return ADL_ERR_INVALID_ARG;
+  uint64_t o_hits, o_btot, o_boff;
+  if (workspace_bytes < hits_ws_layout(num_keys, num_pairs, o_hits, o_btot, o_boff)) return ADL_ERR_WORKSPACE;
+  uint8_t *ws = static_cast<uint8_t *>(d_workspace);
+  uint8_t *ans = ws;
+  uint32_t *hits = reinterpret_cast<uint32_t *>(ws + o_hits);
+  uint64_t *btot = reinterpret_cast<uint64_t *>(ws + o_btot), *boff = reinterpret_cast<uint64_t *>(ws + o_boff);
+  const uint64_t nblk = (num_keys + kBlockP - 1) / kBlockP;
+  const uint32_t k = (uint32_t)adl_host::num_probes(bits_per_key);
+  int rc = dispatch_keys(d_keys, d_offsets, key_stride, [&](auto keys) -> int {
+    const size_t lds = num_filters <= kLdsFilters ? (size_t)num_filters * sizeof(ModLds) : 0;
+    hipLaunchKernelGGL(bloom_probe_fanout_count_kernel<decltype(keys)>, dim3(grid_for(num_keys, kBlockP, 8)),
+                       dim3(kBlockP), lds, st, keys, num_keys, d_pair_begin, d_pair_filter, (uint32_t)num_pairs, k,
+                       d_k, num_filters, d_bitmaps, d_begin, d_end, ans, hits, btot);
+    ADL_HIP_TRY(hipGetLastError());
+    return ADL_OK;
+  });
+  if (rc) return rc;
+  if ((rc = adl_host::level_scan_launch(btot, nblk, boff, d_num_hits, st))) return rc;
+  hipLaunchKernelGGL(fanout_compact_kernel, dim3((uint32_t)nblk), dim3(kBlockP), 0, st, num_keys, d_pair_begin,
+                     d_pair_filter, (uint32_t)num_pairs, ans, hits, boff, d_hit_begin, d_hit_filter, hit_capacity);
+  ADL_HIP_TRY(hipGetLastError());
+  return ADL_OK;
+}
+
+extern "C" uint64_t adl_bloom_probe_fanout_hits_workspace_bytes(uint64_t num_keys, uint64_t num_pairs) {
+  uint64_t a, b, c;
+  return hits_ws_layout(num_keys, num_pairs, a, b, c);
+}
+
+extern "C" int adl_bloom_probe_fanout_hits_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys,
+                                                  uint32_t key_stride, const uint32_t *d_pair_begin,
+                                                  const uint32_t *d_pair_filter, uint64_t num_pairs,
+                                                  uint32_t num_filters, const uint8_t *d_bitmaps,
+                                                  const uint64_t *d_begin, const uint64_t *d_end,
+                                                  int32_t bits_per_key, uint32_t *d_hit_begin,
+                                                  uint32_t *d_hit_filter, uint64_t hit_capacity,
+                                                  uint64_t *d_num_hits, void *d_workspace, uint64_t workspace_bytes,
+                                                  void *stream) {
+  return adl_host::probe_fanout_hits_device(d_keys, d_offsets, num_keys, key_stride, d_pair_begin, d_pair_filter,
+                                            num_pairs, num_filters, d_bitmaps, d_begin, d_end, bits_per_key, nullptr,
+                                            d_hit_begin, d_hit_filter, hit_capacity, d_num_hits, d_workspace,
+                                            workspace_bytes, (hipStream_t)stream);
+}
 
 // adl_bloom_probe_fanout_device with a probe count per filter (d_k[f]), whose
 // launch also completes `done` (the filter cache, as adl_probe_ranges_device_ev).

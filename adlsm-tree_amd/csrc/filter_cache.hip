@@ -644,4 +644,129 @@ int adl_bloom_level_multiget(adl_bloom_level *lv, adl_bloom_filter_cache *c, uin
   }
 }
 
+// The revision multi-get (revision_index.hip): keys and offsets up; selection
+// over every level, expansion, the fan-out probe and the compaction of the
+// hits on the device; the hit lists down.  The tables of all levels are
+// resolved and pinned in ONE pass over the concatenated oid list (global id =
+// table_base[level] + table), so the answers are adl_bloom_level_multiget's,
+// level by level.  The candidate pairs stay in device scratch.
+int adl_bloom_revision_multiget(adl_bloom_revision *rev, adl_bloom_filter_cache *c, uint32_t filter,
+                                const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t num_keys,
+                                uint32_t key_stride, int64_t seq, uint32_t *h_hit_begin, uint32_t *h_hit_table,
+                                uint64_t hit_capacity, uint64_t *num_hits, uint64_t pair_capacity,
+                                uint64_t *num_pairs, uint64_t *h_uncached, void *stream) {
+  if (!rev || !c || !num_hits || !num_pairs || !h_hit_begin) return ADL_ERR_INVALID_ARG;
+  *num_hits = *num_pairs = 0;
+  if (h_uncached) *h_uncached = 0;
+  if (num_keys == 0) {
+    h_hit_begin[0] = 0;
+    return ADL_OK;
+  }
+  if (!h_keys || (!h_offsets && key_stride == 0) || (hit_capacity && !h_hit_table)) return ADL_ERR_INVALID_ARG;
+  const uint32_t num_tables = rev->table_base.back();
+  for (adl_bloom_level *lv : rev->levels)
+    if (lv && lv->ix.num_tables && lv->oids.size() != lv->ix.num_tables) return ADL_ERR_INVALID_ARG;  // no oids
+  if (num_keys >= 0xffffffffull) return ADL_ERR_TOO_LARGE;
+  try {
+    hipStream_t st = adl_host::sync_stream(stream);
+    const uint64_t worst = std::min<uint64_t>(num_keys * (uint64_t)rev->longest, 0xffffffffull);
+    const uint64_t cap = pair_capacity ? std::min<uint64_t>(pair_capacity, 0xffffffffull) : worst;
+    const uint64_t hcap = std::min(hit_capacity, cap);  // (no more hits than pairs)
+    // 1. under the lock: every level's tables' ranges and k, pinned and marked used
+    Resolved &res = t_res;
+    {
+      std::vector<const char *> op;
+      std::vector<uint64_t> ol;
+      op.reserve(num_tables);
+      ol.reserve(num_tables);
+      for (adl_bloom_level *lv : rev->levels) {
+        if (!lv) continue;
+        for (uint32_t t = 0; t < lv->ix.num_tables; ++t) {
+          op.push_back(lv->oids[t].data());
+          ol.push_back(lv->oids[t].size());
+        }
+      }
+      resolve_tables(c, op.data(), ol.data(), num_tables, filter, res);
+    }
+    // 2. without the lock: keys, offsets and the range and k tables in one H2D;
+    //    selection (three launches), probe + hit count, scan, compaction
+    const uint64_t key_bytes = h_offsets ? h_offsets[num_keys] : num_keys * (uint64_t)key_stride;
+    const uint64_t off_bytes = h_offsets ? (num_keys + 1) * 8 : 0;
+    const uint64_t wsc = adl_bloom_revision_candidates_workspace_bytes(rev, num_keys);
+    const uint64_t wsh = adl_bloom_probe_fanout_hits_workspace_bytes(num_keys, cap);
+    const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
+    const uint64_t o_be = o_offs + adl_host::round_up(off_bytes, 256);
+    const uint64_t o_k = o_be + adl_host::round_up(res.be.size() * 8, 256);
+    const uint64_t o_np = o_k + adl_host::round_up(num_tables, 256);  // end of the upload: num_pairs, num_hits
+    const uint64_t o_hb = o_np + 256;
+    const uint64_t o_ht = o_hb + adl_host::round_up((num_keys + 1) * 4, 256);
+    const uint64_t o_pb = o_ht + adl_host::round_up(hcap * 4, 256);  // end of what comes back
+    const uint64_t o_pt = o_pb + adl_host::round_up((num_keys + 1) * 4, 256);
+    const uint64_t o_wsc = o_pt + adl_host::round_up(cap * 4, 256);
+    const uint64_t o_wsh = o_wsc + wsc;
+    const uint64_t total = o_wsh + wsh;
+    adl_host::Staging &sg = adl_host::t_stage;
+    int rc = sg.reserve(o_pb, total);
+    uint8_t *hbuf = sg.host, *dbuf = sg.dev;
+    if (rc == ADL_OK) {
+      if (key_bytes) memcpy(hbuf, h_keys, key_bytes);
+      if (off_bytes) memcpy(hbuf + o_offs, h_offsets, off_bytes);
+      memcpy(hbuf + o_be, res.be.data(), res.be.size() * 8);
+      if (num_tables) memcpy(hbuf + o_k, res.kt.data(), num_tables);
+      if (hipMemcpyAsync(dbuf, hbuf, o_np, hipMemcpyHostToDevice, st) != hipSuccess) rc = ADL_ERR_DEVICE;
+    }
+    const uint64_t *d_offs = h_offsets ? reinterpret_cast<const uint64_t *>(dbuf + o_offs) : nullptr;
+    uint32_t *d_pb = reinterpret_cast<uint32_t *>(dbuf + o_pb), *d_pt = reinterpret_cast<uint32_t *>(dbuf + o_pt);
+    if (rc == ADL_OK)
+      rc = adl_host::revision_select_device(rev, dbuf, d_offs, num_keys, key_stride, seq, d_pb, d_pt, cap,
+                                            reinterpret_cast<uint64_t *>(dbuf + o_np), dbuf + o_wsc, wsc, st);
+    if (rc == ADL_OK) {
+      // (the kernels stop at cap pairs whatever pair_begin says)
+      const uint64_t *d_be = reinterpret_cast<const uint64_t *>(dbuf + o_be);
+      rc = adl_host::probe_fanout_hits_device(dbuf, d_offs, num_keys, key_stride, d_pb, d_pt, cap, num_tables,
+                                              c->arena, d_be, d_be + num_tables, 10, dbuf + o_k,
+                                              reinterpret_cast<uint32_t *>(dbuf + o_hb),
+                                              reinterpret_cast<uint32_t *>(dbuf + o_ht), hcap,
+                                              reinterpret_cast<uint64_t *>(dbuf + o_np + 8), dbuf + o_wsh, wsh, st);
+    }
+    // A batch whose whole result area is small comes back in one copy; a
+    // larger one first learns how many hits there are.
+    const bool one_copy = o_pb - o_np <= (256u << 10);
+    if (rc == ADL_OK &&
+        hipMemcpyAsync(hbuf + o_np, dbuf + o_np, one_copy ? o_pb - o_np : o_ht - o_np, hipMemcpyDeviceToHost, st) !=
+            hipSuccess)
+      rc = ADL_ERR_DEVICE;
+    if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
+    uint64_t np = 0, nh = 0;
+    if (rc == ADL_OK) {
+      memcpy(&np, hbuf + o_np, 8);
+      memcpy(&nh, hbuf + o_np + 8, 8);
+      if (!one_copy && np <= cap && nh && nh <= hcap) {
+        if (hipMemcpyAsync(hbuf + o_ht, dbuf + o_ht, nh * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+          rc = ADL_ERR_DEVICE;
+        if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
+      }
+    }
+    // 3. the kernels and the copies are done: unpin
+    uint64_t uncached = 0;
+    if (rc == ADL_OK && np <= cap && nh <= hcap) {
+      const uint32_t *ht = reinterpret_cast<const uint32_t *>(hbuf + o_ht);
+      for (uint64_t p = 0; p < nh; ++p) uncached += !res.cached[ht[p]];
+    }
+    unpin_tables(c, res);
+    if (rc) return rc;
+    *num_pairs = np;
+    if (np > 0xffffffffull) return ADL_ERR_TOO_LARGE;
+    if (np > cap) return ADL_ERR_WORKSPACE;  // (the hits of the first cap pairs only: nothing else is reported)
+    *num_hits = nh;
+    memcpy(h_hit_begin, hbuf + o_hb, (num_keys + 1) * 4);
+    if (nh > hit_capacity) return ADL_ERR_WORKSPACE;
+    if (nh) memcpy(h_hit_table, hbuf + o_ht, nh * 4);
+    if (h_uncached) *h_uncached = uncached;
+    return ADL_OK;
+  } catch (...) {
+    return ADL_ERR_OUT_OF_MEMORY;
+  }
+}
+
 }  // extern "C"

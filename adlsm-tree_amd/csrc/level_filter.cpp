@@ -233,6 +233,32 @@ uint64_t LevelDeviceMinKeys() {
   return v;
 }
 
+/* The batch size from which RevisionMultiGetFilter makes the one device call,
+ * by the number of non-empty levels; 0 = never.  ADL_BLOOM_REVISION_DEVICE_
+ * MIN_KEYS, or else ADL_BLOOM_LEVEL_DEVICE_MIN_KEYS, where the environment
+ * sets one (read once per process), holds for every revision.
+ * The defaults are the measured crossovers ("Revision
+ * multi-get"; profiles/revision/crossover_summary.txt): the smallest measured
+ * batch from which the single call won on absent-key batches AND on batches
+ * whose every pair is a hit, its worst case (all the pairs come back, as they
+ * do per level).  One level: the call loses 3-32 us up to 2 000 keys and 9 us
+ * on all-hit batches at 4 000, loses 2 us on them at 8 000 and wins 19-47 us
+ * at 16 000.  Two: loses 3-13 us up to
+ * 1 000 keys on all-hit batches, wins 29-46 us at 2 000.  Three: loses 5 us
+ * at 500, wins 21-42 us at 1 000 (four levels were not measured and take
+ * three's).  Five: loses 8 us at 250, wins 14-46 us at 500. */
+uint64_t RevisionDeviceMinKeys(size_t live_levels) {
+  static const int64_t env = [] {
+    for (const char *name : {"ADL_BLOOM_REVISION_DEVICE_MIN_KEYS", "ADL_BLOOM_LEVEL_DEVICE_MIN_KEYS"}) {
+      const char *e = getenv(name);
+      if (e && *e) return (int64_t)strtoull(e, nullptr, 10);
+    }
+    return (int64_t)-1;
+  }();
+  if (env >= 0) return (uint64_t)env;
+  return live_levels <= 1 ? 16000 : live_levels == 2 ? 2000 : live_levels <= 4 ? 1000 : 500;
+}
+
 RC FromStatus(int status) {
   if (status == ADL_OK) return OK;
   if (status == ADL_FILTER_BLOCK_ERROR) return FILTER_BLOCK_ERROR;
@@ -388,7 +414,181 @@ RC LevelMultiGetFilter(FilterCache &cache, LevelIndex &level, const vector<strin
   return OK;
 }
 
+RevisionIndex::RevisionIndex(const vector<LevelIndex *> &levels) : levels_(levels) {
+  table_base_.assign(levels_.size() + 1, 0);
+  if (levels_.size() > ADL_BLOOM_MAX_LEVELS) {
+    status_ = BAD_REVISION;
+    return;
+  }
+  uint64_t longest = 0, tables = 0;
+  for (size_t l = 0; l < levels_.size(); ++l) {
+    const LevelIndex *lv = levels_[l];
+    if (lv && lv->status()) {
+      status_ = lv->status();
+      return;
+    }
+    tables += lv ? lv->tables() : 0;
+    longest += lv && lv->tables() ? lv->longest_list() : 0;
+    table_base_[l + 1] = (uint32_t)tables;
+  }
+  if (tables >= adl_level::kTableMask || longest >= (1u << 24)) status_ = OUT_OF_RANGE;
+  longest_ = (uint32_t)longest;
+}
+
+RevisionIndex::~RevisionIndex() { (void)adl_bloom_revision_destroy(h_); }
+
+adl_bloom_revision *RevisionIndex::handle() {
+  std::call_once(handle_once_, [this] {
+    if (status_) {
+      device_status_ = status_;
+      return;
+    }
+    vector<adl_bloom_level *> hs(levels_.size(), nullptr);
+    for (size_t l = 0; l < levels_.size(); ++l) {
+      if (!levels_[l] || levels_[l]->tables() == 0) continue;
+      hs[l] = levels_[l]->handle();
+      if (!hs[l]) {
+        device_status_ = levels_[l]->device_status();
+        return;
+      }
+    }
+    device_status_ = FromStatus(adl_bloom_revision_create(hs.data(), (uint32_t)hs.size(), &h_));
+  });
+  return h_;
+}
+
+void RevisionIndex::Candidates(const vector<string_view> &user_keys, int64_t seq, vector<uint32_t> &begin,
+                               vector<uint32_t> &table) const {
+  const size_t K = user_keys.size(), L = levels_.size();
+  begin.assign(K + 1, 0);
+  table.clear();
+  if (status_) return;
+  vector<vector<uint32_t>> lb(L), lt(L);
+  for (size_t l = 0; l < L; ++l)
+    if (levels_[l] && levels_[l]->tables()) levels_[l]->Candidates(user_keys, seq, lb[l], lt[l]);
+  for (size_t i = 0; i < K; ++i) {
+    for (size_t l = 0; l < L; ++l) {
+      if (lb[l].empty()) continue;
+      for (uint32_t p = lb[l][i]; p < lb[l][i + 1]; ++p) table.push_back(table_base_[l] + lt[l][p]);
+    }
+    begin[i + 1] = (uint32_t)table.size();
+  }
+}
+
+RC RevisionMultiGetFilter(FilterCache &cache, RevisionIndex &rev, const vector<string_view> &user_keys, int64_t seq,
+                          RevisionMultiGetResult &out) {
+  out = RevisionMultiGetResult{};
+  if (rev.status()) return rev.status();
+  const size_t K = user_keys.size(), L = rev.levels();
+  const vector<uint32_t> &base = rev.table_base();
+  out.begin.assign(K + 1, 0);
+  auto fill_levels = [&] {
+    out.level.resize(out.table.size());
+    for (size_t p = 0; p < out.table.size(); ++p)
+      out.level[p] = (uint8_t)(std::upper_bound(base.begin(), base.end(), out.table[p]) - base.begin() - 1);
+  };
+  size_t live = 0;
+  for (size_t l = 0; l < L; ++l) live += rev.level(l) && rev.level(l)->tables();
+  const uint64_t min_keys = RevisionDeviceMinKeys(live);
+  if (min_keys == 0 || K < min_keys) {
+    // one level multi-get per level, then the pass that keeps the hits
+    vector<MultiGetFilterResult> per(L);
+    for (size_t l = 0; l < L; ++l) {
+      LevelIndex *lv = rev.level(l);
+      if (!lv || lv->tables() == 0) continue;
+      if (RC rc = LevelMultiGetFilter(cache, *lv, user_keys, seq, per[l])) {
+        out = RevisionMultiGetResult{};
+        return rc;
+      }
+    }
+    for (size_t i = 0; i < K; ++i) {
+      for (size_t l = 0; l < L; ++l) {
+        const MultiGetFilterResult &r = per[l];
+        if (r.begin.empty()) continue;
+        for (uint32_t p = r.begin[i]; p < r.begin[i + 1]; ++p)
+          if (r.maybe[p]) out.table.push_back(base[l] + r.table[p]);
+      }
+      out.begin[i + 1] = (uint32_t)out.table.size();
+    }
+    // a table that is not cached answers 1 for every pair: its pairs are all hits
+    for (size_t l = 0; l < L; ++l) out.uncached += per[l].uncached;
+    fill_levels();
+    return OK;
+  }
+  adl_bloom_revision *h = rev.handle();
+  if (!h) return rev.device_status();
+  if (!cache.handle()) return cache.status();
+  size_t key_bytes = 0;
+  for (string_view k : user_keys) key_bytes += k.size();
+  KeyArena batch;
+  batch.Reserve(K, key_bytes);
+  for (string_view k : user_keys) batch.Add(k);
+  // Scratch for twice the mean lists per key first, as the level overload
+  // sizes its buffers, and the exact sizes, which the call reports, where a
+  // batch needs more.
+  const uint64_t worst = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)K * rev.longest_list(), 0xffffffffull));
+  uint64_t mean = 0;
+  for (size_t l = 0; l < L; ++l)
+    if (rev.level(l) && rev.level(l)->tables()) mean += rev.level(l)->mean_list();
+  uint64_t pcap = std::min<uint64_t>(worst, 2ull * K * mean + 1024), hcap = pcap;
+  uint64_t np = 0, nh = 0;
+  int st = ADL_OK;
+  for (int attempt = 0; attempt < 3; ++attempt) {
+    out.table.resize(hcap);
+    st = adl_bloom_revision_multiget(h, cache.handle(), 0, reinterpret_cast<const uint8_t *>(batch.bytes().data()),
+                                     batch.offsets().data(), K, 0, seq, out.begin.data(), out.table.data(), hcap,
+                                     &nh, pcap, &np, &out.uncached, nullptr);
+    if (st != ADL_ERR_WORKSPACE || np > worst) break;
+    if (np > pcap) pcap = np;
+    else if (nh > hcap) hcap = nh;
+    else break;
+  }
+  if (st != ADL_OK) {
+    out = RevisionMultiGetResult{};
+    return FromStatus(st);
+  }
+  out.table.resize(nh);
+  fill_levels();
+  return OK;
+}
+
 }  // namespace adl
+
+/* Test hook (tests/test_revision_cpu.py): one LevelIndex per level over its
+ * tables, a RevisionIndex over them, and its host Candidates for one batch.
+ * Level l's tables are [table_begin[l], table_begin[l+1]) of mins / maxs; a
+ * level with skip[l] != 0 is handed over as nullptr.  begin: K+1 entries,
+ * table: up to cap global ids.  Returns the number of pairs, -1 when cap is
+ * too small, -2 when an index was not built. */
+extern "C" int64_t adl_revision_index_candidates(const char *const *mins, const uint64_t *min_lens,
+                                                 const char *const *maxs, const uint64_t *max_lens,
+                                                 const uint32_t *table_begin, const uint8_t *skip, uint32_t L,
+                                                 const char *const *keys, const uint64_t *key_lens, uint32_t K,
+                                                 int64_t seq, uint32_t *begin, uint32_t *table, uint64_t cap) {
+  std::vector<std::unique_ptr<adl::LevelIndex>> own(L);
+  std::vector<adl::LevelIndex *> lv(L, nullptr);
+  for (uint32_t l = 0; l < L; ++l) {
+    if (skip && skip[l]) continue;
+    std::vector<adl::TableRange> tabs;
+    for (uint32_t t = table_begin[l]; t < table_begin[l + 1]; ++t) {
+      tabs.emplace_back();
+      tabs.back().min_inner_key.assign(mins[t], min_lens[t]);
+      tabs.back().max_inner_key.assign(maxs[t], max_lens[t]);
+    }
+    own[l] = std::make_unique<adl::LevelIndex>(tabs);
+    lv[l] = own[l].get();
+  }
+  adl::RevisionIndex rev(lv);
+  if (rev.status()) return -2;
+  std::vector<std::string_view> ks(K);
+  for (uint32_t i = 0; i < K; ++i) ks[i] = std::string_view(keys[i], key_lens[i]);
+  std::vector<uint32_t> b, tb;
+  rev.Candidates(ks, seq, b, tb);
+  if (tb.size() > cap) return -1;
+  std::copy(b.begin(), b.end(), begin);
+  std::copy(tb.begin(), tb.end(), table);
+  return (int64_t)tb.size();
+}
 
 /* Test hook (tests/test_level_cpu.py): LevelCandidates over tables and keys
  * handed over as (pointer, length) arrays; begin: K+1 entries, table: up to

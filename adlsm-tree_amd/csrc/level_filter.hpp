@@ -29,6 +29,7 @@
 #include "rc.hpp"
 
 struct adl_bloom_level;
+struct adl_bloom_revision;
 namespace adl_level {
 struct Index;
 }
@@ -142,5 +143,64 @@ class LevelIndex {
  * on the device (adl_bloom_level_multiget). */
 RC LevelMultiGetFilter(FilterCache &cache, LevelIndex &level, const vector<string_view> &user_keys, int64_t seq,
                        MultiGetFilterResult &out);
+
+/* The whole revision: its levels in Revision::Get's visiting order
+ * (src/revision.cpp:391-403), level 0 first.  The LevelIndex objects are
+ * BORROWED and must outlive it; nullptr or a level of no tables is an empty
+ * level (skipped, as levels_[i].Empty() is).  Table t of level l has the
+ * global id table_base()[l] + t.  status(): BAD_REVISION for more than
+ * ADL_BLOOM_MAX_LEVELS (8) levels, a level's own status, OUT_OF_RANGE when the
+ * levels' longest lists sum to 2^24 or more. */
+class RevisionIndex {
+ public:
+  explicit RevisionIndex(const vector<LevelIndex *> &levels);
+  ~RevisionIndex();
+  RevisionIndex(const RevisionIndex &) = delete;
+  RevisionIndex &operator=(const RevisionIndex &) = delete;
+  RC status() const { return status_; }
+  size_t levels() const { return levels_.size(); }
+  LevelIndex *level(size_t l) const { return levels_[l]; }
+  const vector<uint32_t> &table_base() const { return table_base_; } /* levels() + 1 entries */
+  uint32_t longest_list() const { return longest_; }                /* no key has more candidates */
+  /* Every level's LevelIndex::Candidates, concatenated per key, level 0
+   * first, as global ids (host only) */
+  void Candidates(const vector<string_view> &user_keys, int64_t seq, vector<uint32_t> &begin,
+                  vector<uint32_t> &table) const;
+  /* The C-ABI revision over the levels' handles, made by the first call: NULL
+   * when that failed (device_status()). */
+  adl_bloom_revision *handle();
+  RC device_status() const { return device_status_; }
+
+ private:
+  vector<LevelIndex *> levels_;
+  vector<uint32_t> table_base_;
+  uint32_t longest_ = 0;
+  std::once_flag handle_once_;
+  adl_bloom_revision *h_ = nullptr;
+  RC device_status_ = OK;
+  RC status_ = OK;
+};
+
+struct RevisionMultiGetResult {
+  vector<uint32_t> begin; /* key i's hits: [begin[i], begin[i+1]) */
+  vector<uint32_t> table; /* global ids of the tables still to read, in Revision::Get's visiting order */
+  vector<uint8_t> level;  /* the level of each hit */
+  uint64_t uncached = 0;  /* hits whose table was not in the cache (answered 1) */
+};
+
+/* The filter stage of Revision::Get for a batch: per key, the tables of all
+ * levels that cover it and whose filter does not rule it out, levels
+ * ascending, within a level in Level::Get's order.  The caller reads them in
+ * that order and stops at the first that holds the key.  Small batches run
+ * LevelMultiGetFilter(cache, LevelIndex&, ...) once per level and keep the
+ * pairs answered 1; larger ones are ONE call (adl_bloom_revision_multiget):
+ * keys up, hits down.  Both give the same result.  The threshold is
+ * ADL_BLOOM_REVISION_DEVICE_MIN_KEYS, or else ADL_BLOOM_LEVEL_DEVICE_MIN_KEYS,
+ * where the environment sets one (0 = never the single call); otherwise the
+ * measured crossover for the revision's number of non-empty levels: 16 000
+ * keys for one, 2 000 for two, 1 000 for three or four, 500 from five on
+ * (DESIGN.md §5). */
+RC RevisionMultiGetFilter(FilterCache &cache, RevisionIndex &rev, const vector<string_view> &user_keys, int64_t seq,
+                          RevisionMultiGetResult &out);
 
 }  // namespace adl

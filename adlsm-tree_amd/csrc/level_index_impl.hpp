@@ -1,6 +1,7 @@
-// adlsm-tree_amd/csrc/level_index_impl.hpp -- adl_bloom_level as
-// level_index.hip (index, kernels, selection) and filter_cache.hip (the
-// multi-get through a cache) share it.
+// adlsm-tree_amd/csrc/level_index_impl.hpp -- adl_bloom_level and
+// adl_bloom_revision as level_index.hip and revision_index.hip (index, kernels,
+// selection), bloom_probe.hip (the hit kernels' scan) and filter_cache.hip (the
+// multi-gets through a cache) share them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,5 +44,51 @@ __attribute__((visibility("hidden"))) int level_select_device(adl_bloom_level *l
                                                               uint64_t pair_capacity, uint64_t *d_num_pairs,
                                                               void *d_workspace, uint64_t workspace_bytes,
                                                               hipStream_t st);
+
+// The level's device copy, made if this is its first device call (revision_index.hip).
+__attribute__((visibility("hidden"))) int level_ensure_uploaded(adl_bloom_level *lv);
+
+// level_scan_kernel on `st`: d_block_off = the exclusive scan of nblk u64
+// block totals, *d_total their sum (revision_index.hip, bloom_probe.hip).
+__attribute__((visibility("hidden"))) int level_scan_launch(const uint64_t *d_block_total, uint64_t nblk,
+                                                            uint64_t *d_block_off, uint64_t *d_total,
+                                                            hipStream_t st);
+
+}  // namespace adl_host
+
+// A revision: its levels in Revision::Get's visiting order, borrowed.  The
+// host part is immutable after creation; the device copy (`d_blob`: the
+// non-empty levels' descriptors and table bases, revision_index.hip) is made by
+// the first device call, under `mu`.
+struct adl_bloom_revision {
+  std::vector<adl_bloom_level *> levels;  // as given; NULL or 0 tables: an empty level
+  std::vector<uint32_t> table_base;       // levels.size() + 1
+  uint32_t longest = 0;                   // the sum of the levels' longest lists
+  std::mutex mu;
+  bool uploaded = false;
+  int upload_status = 0;
+  uint8_t *d_blob = nullptr;
+  uint32_t live = 0;  // non-empty levels (what the device copy describes)
+};
+
+namespace adl_host {
+
+// adl_bloom_revision_candidates_device after its argument checks.
+__attribute__((visibility("hidden"))) int revision_select_device(adl_bloom_revision *rev, const uint8_t *d_keys,
+                                                                 const uint64_t *d_offsets, uint64_t num_keys,
+                                                                 uint32_t key_stride, int64_t seq,
+                                                                 uint32_t *d_pair_begin, uint32_t *d_pair_table,
+                                                                 uint64_t pair_capacity, uint64_t *d_num_pairs,
+                                                                 void *d_workspace, uint64_t workspace_bytes,
+                                                                 hipStream_t st);
+
+// adl_bloom_probe_fanout_hits_device with a probe count per filter (d_k[f];
+// NULL: the k of bits_per_key), bloom_probe.hip.
+__attribute__((visibility("hidden"))) int probe_fanout_hits_device(
+    const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys, uint32_t key_stride,
+    const uint32_t *d_pair_begin, const uint32_t *d_pair_filter, uint64_t num_pairs, uint32_t num_filters,
+    const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end, int32_t bits_per_key,
+    const uint8_t *d_k, uint32_t *d_hit_begin, uint32_t *d_hit_filter, uint64_t hit_capacity, uint64_t *d_num_hits,
+    void *d_workspace, uint64_t workspace_bytes, hipStream_t st);
 
 }  // namespace adl_host

@@ -414,6 +414,99 @@ int adl_bloom_level_multiget(adl_bloom_level *level, adl_bloom_filter_cache *cac
                              uint8_t *h_out, uint64_t pair_capacity, uint64_t *num_pairs, uint64_t *h_uncached,
                              void *stream);
 
+/* ------------------------------------------- revision multi-get */
+
+/* The whole revision asked once.  Revision::Get (src/revision.cpp:391-403)
+ * walks its levels in order, level 0 first, skips a level that is Empty() and
+ * calls Level::Get on the others until one finds the key.  A revision here is
+ * the list of its levels' resident indices, in that visiting order; the levels
+ * are BORROWED and must outlive it.  A NULL entry or a level of 0 tables is an
+ * empty level.  Table t of level l has the GLOBAL id table_base[l] + t, where
+ * table_base[l] counts the tables of the levels before l; every call below
+ * reports global ids.  create, destroy and stats need no GPU; the device copy
+ * (the non-empty levels' descriptors and bases) is made by the first device
+ * call, which also makes each level's own copy. */
+#define ADL_BLOOM_MAX_LEVELS 8
+typedef struct adl_bloom_revision adl_bloom_revision;
+
+/* ADL_ERR_INVALID_ARG: more than ADL_BLOOM_MAX_LEVELS levels.
+ * ADL_ERR_TOO_LARGE: 2^31 - 1 tables or more in all, or the levels'
+ * longest_list values sum to 2^24 or more (256 keys' lists add up in a u32,
+ * as within one level). */
+int adl_bloom_revision_create(adl_bloom_level *const *levels, uint32_t num_levels, adl_bloom_revision **rev);
+/* No call on the revision may be running or start once this is called.  The
+ * levels stay the caller's. */
+int adl_bloom_revision_destroy(adl_bloom_revision *rev);
+/* table_base: num_levels + 1 entries (the last: the tables of all levels).
+ * *longest_list: the sum over the levels -- no key has more candidates, so
+ * num_keys * *longest_list pairs always suffice.  Each optional. */
+int adl_bloom_revision_stats(const adl_bloom_revision *rev, uint32_t *num_levels, uint32_t *table_base,
+                             uint32_t *longest_list);
+
+/* Selection over all levels on the device: key i's list is the concatenation,
+ * level 0 first, of what adl_bloom_level_candidates_device gives for each
+ * level at `seq`, as global ids.  The contract is that call's in every other
+ * respect: d_pair_begin (num_keys+1 u32) always complete, entries from
+ * pair_capacity on not written, *d_num_pairs the u64 total, no byte outside a
+ * key read, stream-ordered with no synchronisation apart from the first call's
+ * upload.  The number of launches does not depend on the number of levels.
+ * Revision::Get takes a seq but does not pass it on (levels_[i].Get(key,
+ * value), src/revision.cpp:395: Level::Get's default, INT64_MAX), so seq =
+ * INT64_MAX reproduces the reference's Revision::Get itself.  d_workspace:
+ * 256-byte aligned, adl_bloom_revision_candidates_workspace_bytes(rev,
+ * num_keys) bytes. */
+uint64_t adl_bloom_revision_candidates_workspace_bytes(const adl_bloom_revision *rev, uint64_t num_keys);
+int adl_bloom_revision_candidates_device(adl_bloom_revision *rev, const uint8_t *d_keys, const uint64_t *d_offsets,
+                                         uint64_t num_keys, uint32_t key_stride, int64_t seq,
+                                         uint32_t *d_pair_begin, uint32_t *d_pair_table, uint64_t pair_capacity,
+                                         uint64_t *d_num_pairs, void *d_workspace, uint64_t workspace_bytes,
+                                         void *stream);
+
+/* The fan-out probe that returns the survivors only: the inputs of
+ * adl_bloom_probe_fanout_device; key i's hits are d_hit_filter[d_hit_begin[i]
+ * .. d_hit_begin[i+1]), the d_pair_filter[p] of exactly those pairs p of key i
+ * that adl_bloom_probe_fanout_device answers 1 for, in pair order.
+ * d_hit_begin (num_keys+1 u32) is always complete and *d_num_hits (a device
+ * u64) the total; entries from hit_capacity on are not written.  The output is
+ * deterministic (a stable compaction: no atomic decides an order).
+ * Stream-ordered, three launches; num_keys == 0 launches none.  d_workspace:
+ * 256-byte aligned, adl_bloom_probe_fanout_hits_workspace_bytes(num_keys,
+ * num_pairs) bytes (it holds the answer bytes). */
+uint64_t adl_bloom_probe_fanout_hits_workspace_bytes(uint64_t num_keys, uint64_t num_pairs);
+int adl_bloom_probe_fanout_hits_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys,
+                                       uint32_t key_stride, const uint32_t *d_pair_begin,
+                                       const uint32_t *d_pair_filter, uint64_t num_pairs, uint32_t num_filters,
+                                       const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end,
+                                       int32_t bits_per_key, uint32_t *d_hit_begin, uint32_t *d_hit_filter,
+                                       uint64_t hit_capacity, uint64_t *d_num_hits, void *d_workspace,
+                                       uint64_t workspace_bytes, void *stream);
+
+/* Revision multi-get: uploads the keys (and offsets) only; selection over
+ * every level, list expansion, the probes and the compaction of the hits run
+ * on the device; h_hit_begin (num_keys+1) and h_hit_table come back: per key
+ * the tables it still has to read, as global ids, the levels ascending and
+ * within a level in Level::Get's order -- the order Revision::Get visits them
+ * in.  The candidate pairs never leave the device: pair_capacity sizes their
+ * scratch (0: min(num_keys * the revision's longest_list, 2^32-1)) and
+ * *num_pairs reports their total; a total above pair_capacity is
+ * ADL_ERR_WORKSPACE with *num_pairs set and nothing else written, one of 2^32
+ * or more ADL_ERR_TOO_LARGE.  *num_hits above hit_capacity is
+ * ADL_ERR_WORKSPACE with h_hit_begin complete.  The oids of all levels are
+ * resolved and pinned in `cache` in one pass (a level created without oids:
+ * ADL_ERR_INVALID_ARG); a table that is not cached answers 1, so it is a hit,
+ * and *h_uncached counts such hits; a filter the block does not have answers
+ * 0; each table is probed with the k of its own block, as
+ * adl_bloom_level_multiget does.  num_keys == 0 launches nothing.
+ * Synchronous.  Replaces Revision::Get's loop over the levels
+ * (src/revision.cpp:391-403) up to the tables' filter checks for a batch of
+ * lookup keys; reading the tables, and stopping at the first that holds the
+ * key, stay with the caller, who walks the hits in order. */
+int adl_bloom_revision_multiget(adl_bloom_revision *rev, adl_bloom_filter_cache *cache, uint32_t filter,
+                                const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t num_keys,
+                                uint32_t key_stride, int64_t seq, uint32_t *h_hit_begin, uint32_t *h_hit_table,
+                                uint64_t hit_capacity, uint64_t *num_hits, uint64_t pair_capacity,
+                                uint64_t *num_pairs, uint64_t *h_uncached, void *stream);
+
 /* ------------------------------------------- write-through builds into the cache */
 
 /* A table's filter block built straight into a reserved range of the cache
