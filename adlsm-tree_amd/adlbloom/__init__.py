@@ -644,6 +644,19 @@ class FilterSet:
             pass
 
 
+def _host_keys(keys, offsets):
+    """Host keys (and offsets) as the C-ABI takes them: (arrays to keep alive, key pointer, offsets pointer or
+    None, n, stride).  A batch of no key bytes still has an address."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    if offsets is None:
+        n, stride, po = keys.shape[0], keys.shape[1], None
+    else:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n, stride, po = len(offsets) - 1, 0, offsets.ctypes.data
+    kbuf = keys if keys.size else np.zeros(16, np.uint8)
+    return (kbuf, offsets), kbuf.ctypes.data, po, n, stride
+
+
 class FilterCache:
     """Device-resident filter blocks keyed by SSTable oid, LRU (adl_bloom_filter_cache)."""
 
@@ -674,19 +687,14 @@ class FilterCache:
 
     def probe(self, oids, table, keys: np.ndarray, offsets=None, filter: int = 0, stream=None):
         """Query i against filter `filter` of table oids[table[i]]; returns (0/1 array, uncached count)."""
-        keys = np.ascontiguousarray(keys, dtype=np.uint8)
-        if offsets is None:
-            n, stride, po = keys.shape[0], keys.shape[1], None
-        else:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n, stride, po = len(offsets) - 1, 0, offsets.ctypes.data
+        keep, kp, po, n, stride = _host_keys(keys, offsets)
         arr = (ctypes.c_char_p * max(len(oids), 1))(*oids)
         lens = np.array([len(o) for o in oids] or [0], dtype=np.uint64)
         tab = np.ascontiguousarray(table, dtype=np.uint32)
         out = np.empty(max(n, 1), dtype=np.uint8)
         unc = ctypes.c_uint64()
         _check(lib().adl_bloom_filter_cache_probe(self._h, arr, lens.ctypes.data, len(oids), filter,
-                                                  keys.ctypes.data, po, n, stride, tab.ctypes.data,
+                                                  kp, po, n, stride, tab.ctypes.data,
                                                   out.ctypes.data, ctypes.byref(unc), _host_stream(stream)),
                "adl_bloom_filter_cache_probe")
         return out[:n], unc.value
@@ -696,12 +704,7 @@ class FilterCache:
         """Key i against filter `filter` of every table oids[t], t in pair_table[pair_begin[i]:pair_begin[i+1]];
         returns (0/1 per pair in pair order, uncached pair count): probe() on the expanded pairs, each key
         uploaded and hashed once."""
-        keys = np.ascontiguousarray(keys, dtype=np.uint8)
-        if offsets is None:
-            n, stride, po = keys.shape[0], keys.shape[1], None
-        else:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n, stride, po = len(offsets) - 1, 0, offsets.ctypes.data
+        keep, kp, po, n, stride = _host_keys(keys, offsets)
         arr = (ctypes.c_char_p * max(len(oids), 1))(*oids)
         lens = np.array([len(o) for o in oids] or [0], dtype=np.uint64)
         pb = np.ascontiguousarray(pair_begin, dtype=np.uint32)
@@ -712,7 +715,6 @@ class FilterCache:
             raise ValueError("pair_begin[-1] must equal len(pair_table)")
         out = np.empty(max(len(tab), 1), dtype=np.uint8)
         unc = ctypes.c_uint64()
-        kp = keys.ctypes.data if keys.size else np.zeros(1, np.uint8).ctypes.data
         _check(lib().adl_bloom_filter_cache_probe_fanout(self._h, arr, lens.ctypes.data, len(oids), filter, kp, po,
                                                          n, stride, pb.ctypes.data, tab.ctypes.data, out.ctypes.data,
                                                          ctypes.byref(unc), _host_stream(stream)),
@@ -856,17 +858,6 @@ class LevelIndex:
                                            ctypes.byref(lg)), "adl_bloom_level_stats")
         return r.value, e.value, b.value, lg.value
 
-    @staticmethod
-    def _host_keys(keys, offsets):
-        keys = np.ascontiguousarray(keys, dtype=np.uint8)
-        if offsets is None:
-            n, stride, po = keys.shape[0], keys.shape[1], None
-        else:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            n, stride, po = len(offsets) - 1, 0, offsets.ctypes.data
-        kp = keys.ctypes.data if keys.size else np.zeros(16, np.uint8).ctypes.data
-        return (keys, offsets), kp, po, n, stride
-
     def candidates_device(self, keys, offsets=None, seq: int = 2**63 - 1, pair_capacity: int | None = None,
                           stream=None):
         """Selection on the device from torch device tensors, enqueued on `stream` without a synchronise:
@@ -889,7 +880,7 @@ class LevelIndex:
     def multiget_status(self, cache: "FilterCache", keys: np.ndarray, offsets=None, seq: int = 2**63 - 1,
                         filter: int = 0, pair_capacity: int | None = None, stream=None):
         """adl_bloom_level_multiget: (status, pair_begin, pair_table, answers, num_pairs, uncached)."""
-        keep, kp, po, n, stride = self._host_keys(keys, offsets)
+        keep, kp, po, n, stride = _host_keys(keys, offsets)
         cap = n * self.stats()[3] if pair_capacity is None else int(pair_capacity)
         pb = np.zeros(n + 1, dtype=np.uint32)
         pt = np.zeros(max(cap, 1), dtype=np.uint32)
@@ -965,7 +956,7 @@ class Revision:
                         filter: int = 0, hit_capacity: int | None = None, pair_capacity: int = 0, stream=None):
         """adl_bloom_revision_multiget: (status, hit_begin, hit_table, num_hits, num_pairs, uncached).
         hit_capacity: default n * the longest list."""
-        keep, kp, po, n, stride = LevelIndex._host_keys(keys, offsets)
+        keep, kp, po, n, stride = _host_keys(keys, offsets)
         cap = n * self.stats()[2] if hit_capacity is None else int(hit_capacity)
         hb = np.zeros(n + 1, dtype=np.uint32)
         ht = np.zeros(max(cap, 1), dtype=np.uint32)

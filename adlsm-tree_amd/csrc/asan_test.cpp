@@ -280,6 +280,10 @@ void LevelIndexChecks() {
   lw.Candidates(kv, INT64_MAX, bw, tw);
   l1.Candidates(kv, INT64_MAX, b1, t1);
   CHECK(b.size() == 5 && b[4] == t.size() && t.size() == tw.size() + 2 * t1.size());
+  // (four keys on `wide`: its lists outgrow 4 x 64 range tests, so LevelCandidates scans the tables directly)
+  std::vector<uint32_t> bd, td;
+  LevelCandidates(wide, kv, INT64_MAX, bd, td);
+  CHECK(bd == bw && td == tw);
   for (size_t i = 0; i < kv.size(); ++i) {
     std::vector<uint32_t> want(t1.begin() + b1[i], t1.begin() + b1[i + 1]);
     for (uint32_t p = bw[i]; p < bw[i + 1]; ++p) want.push_back(1 + tw[p]);

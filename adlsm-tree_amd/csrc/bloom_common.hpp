@@ -340,6 +340,40 @@ struct Staging {
 
 inline thread_local Staging t_stage;
 
+// The layout of a staging buffer (or a workspace, or a blob uploaded once):
+// sections handed out one after another, each starting 256-byte aligned.
+// `end` is where the next one would start: the bytes an upload of everything
+// placed so far moves, and at last the size to reserve.
+struct StagePlan {
+  uint64_t end = 0;
+  uint64_t take(uint64_t bytes) {
+    const uint64_t at = end;
+    end += round_up(bytes, 256);
+    return at;
+  }
+};
+
+// The key block every host-pointer entry point stages first, at offset 0 of a
+// plan with nothing placed yet: the key bytes (+16: a kernel's wide loads of
+// the last key stay inside the section), then the n + 1 offsets (no section
+// for a fixed stride).
+struct KeyBlock {
+  uint64_t key_bytes, off_bytes, o_offs;
+  KeyBlock(StagePlan &p, const uint64_t *h_offsets, uint64_t n, uint32_t key_stride)
+      : key_bytes(h_offsets ? h_offsets[n] : n * (uint64_t)key_stride), off_bytes(h_offsets ? (n + 1) * 8 : 0) {
+    p.take(key_bytes + 16);
+    o_offs = p.take(off_bytes);
+  }
+  void fill(uint8_t *hbuf, const uint8_t *h_keys, const uint64_t *h_offsets) const {
+    if (key_bytes) memcpy(hbuf, h_keys, key_bytes);
+    if (off_bytes) memcpy(hbuf + o_offs, h_offsets, off_bytes);
+  }
+  // the device offsets of a buffer laid out by the plan (null: fixed stride)
+  const uint64_t *offsets(const uint8_t *dbuf) const {
+    return off_bytes ? reinterpret_cast<const uint64_t *>(dbuf + o_offs) : nullptr;
+  }
+};
+
 // Per-thread small pinned buffer mapped into the device's address space
 // (coherent): a small synchronous probe hands the kernel its keys and table
 // ids where they are and has it write the answers back there, so a lookup is

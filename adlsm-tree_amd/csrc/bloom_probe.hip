@@ -538,6 +538,25 @@ extern "C" int adl_bloom_probe_ranges_device(const uint8_t *d_keys, const uint64
                      bits_per_key, d_out, (hipStream_t)stream, d_end);
 }
 
+namespace {
+
+// The end of a staged host-pointer probe whose launch returned rc: its n
+// answers come from sg.dev + o_out through the front of the host buffer (the
+// upload is done with it) to h_out.  The stream is idle on return.
+int fetch_answers(adl_host::Staging &sg, uint64_t o_out, uint64_t n, hipStream_t st, int rc, uint8_t *h_out) {
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  if (hipMemcpyAsync(sg.host, sg.dev + o_out, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return ADL_ERR_DEVICE;
+  memcpy(h_out, sg.host, n);
+  return ADL_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int adl_bloom_probe_multi_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n,
@@ -558,30 +577,19 @@ int adl_bloom_probe(const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t n
   if (!h_keys || !h_bitmap || !h_out) return ADL_ERR_INVALID_ARG;
   if (!h_offsets && key_stride == 0) return ADL_ERR_INVALID_ARG;
   hipStream_t st = adl_host::sync_stream(stream);
-  const uint64_t key_bytes = h_offsets ? h_offsets[n] : n * (uint64_t)key_stride;
-  const uint64_t off_bytes = h_offsets ? (n + 1) * 8 : 0;
-  const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
-  const uint64_t o_bm = o_offs + adl_host::round_up(off_bytes, 256);
-  const uint64_t o_out = o_bm + adl_host::round_up(bitmap_bytes, 256);
-  const uint64_t total = o_out + adl_host::round_up(n, 256);
+  adl_host::StagePlan plan;
+  const adl_host::KeyBlock kb(plan, h_offsets, n, key_stride);
+  const uint64_t o_bm = plan.take(bitmap_bytes);
+  const uint64_t o_out = plan.take(n);  // the end of the upload
   adl_host::Staging &sg = adl_host::t_stage;
-  int rc = sg.reserve(o_out, total);
+  int rc = sg.reserve(o_out, plan.end);
   if (rc) return rc;
-  if (key_bytes) memcpy(sg.host, h_keys, key_bytes);
-  if (off_bytes) memcpy(sg.host + o_offs, h_offsets, off_bytes);
+  kb.fill(sg.host, h_keys, h_offsets);
   memcpy(sg.host + o_bm, h_bitmap, bitmap_bytes);
   if (hipMemcpyAsync(sg.dev, sg.host, o_out, hipMemcpyHostToDevice, st) != hipSuccess) return ADL_ERR_DEVICE;
-  rc = adl_bloom_probe_device(sg.dev, h_offsets ? reinterpret_cast<uint64_t *>(sg.dev + o_offs) : nullptr, n,
-                              key_stride, bits_per_key, sg.dev + o_bm, bitmap_bytes, sg.dev + o_out, st);
-  if (rc) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  if (hipMemcpyAsync(sg.host, sg.dev + o_out, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return ADL_ERR_DEVICE;
-  memcpy(h_out, sg.host, n);
-  return ADL_OK;
+  rc = adl_bloom_probe_device(sg.dev, kb.offsets(sg.dev), n, key_stride, bits_per_key, sg.dev + o_bm, bitmap_bytes,
+                              sg.dev + o_out, st);
+  return fetch_answers(sg, o_out, n, st, rc, h_out);
 }
 
 int adl_bloom_murmur3_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n,
@@ -719,31 +727,20 @@ int adl_bloom_filter_set_probe(const adl_bloom_filter_set *set, const uint8_t *h
   if (n == 0) return ADL_OK;
   if (!h_keys || !h_out || (!h_offsets && key_stride == 0)) return ADL_ERR_INVALID_ARG;
   hipStream_t st = adl_host::sync_stream(stream);
-  const uint64_t key_bytes = h_offsets ? h_offsets[n] : n * (uint64_t)key_stride;
-  const uint64_t off_bytes = h_offsets ? (n + 1) * 8 : 0;
-  const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
-  const uint64_t o_fid = o_offs + adl_host::round_up(off_bytes, 256);
-  const uint64_t o_out = o_fid + adl_host::round_up(h_filter_id ? n * 4 : 0, 256);
-  const uint64_t total = o_out + adl_host::round_up(n, 256);
+  adl_host::StagePlan plan;
+  const adl_host::KeyBlock kb(plan, h_offsets, n, key_stride);
+  const uint64_t o_fid = plan.take(h_filter_id ? n * 4 : 0);
+  const uint64_t o_out = plan.take(n);  // the end of the upload
   adl_host::Staging &sg = adl_host::t_stage;
-  int rc = sg.reserve(o_out, total);
+  int rc = sg.reserve(o_out, plan.end);
   if (rc) return rc;
-  if (key_bytes) memcpy(sg.host, h_keys, key_bytes);
-  if (off_bytes) memcpy(sg.host + o_offs, h_offsets, off_bytes);
+  kb.fill(sg.host, h_keys, h_offsets);
   if (h_filter_id) memcpy(sg.host + o_fid, h_filter_id, n * 4);
   if (hipMemcpyAsync(sg.dev, sg.host, o_out, hipMemcpyHostToDevice, st) != hipSuccess) return ADL_ERR_DEVICE;
-  rc = probe_multi(sg.dev, h_offsets ? reinterpret_cast<uint64_t *>(sg.dev + o_offs) : nullptr, n, key_stride,
+  rc = probe_multi(sg.dev, kb.offsets(sg.dev), n, key_stride,
                    h_filter_id ? reinterpret_cast<uint32_t *>(sg.dev + o_fid) : nullptr, filter, set->nf,
                    set->d_bitmaps, set->d_off, set->bpk, sg.dev + o_out, st);
-  if (rc) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  if (hipMemcpyAsync(sg.host, sg.dev + o_out, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    return ADL_ERR_DEVICE;
-  memcpy(h_out, sg.host, n);
-  return ADL_OK;
+  return fetch_answers(sg, o_out, n, st, rc, h_out);
 }
 
 int adl_bloom_filter_set_device_view(const adl_bloom_filter_set *set, const uint8_t **d_bitmaps,

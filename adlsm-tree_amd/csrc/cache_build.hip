@@ -563,26 +563,24 @@ int adl_bloom_verify(const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t 
   if (bm_bytes && !h_bitmaps) return ADL_ERR_INVALID_ARG;
   try {
     hipStream_t st = adl_host::sync_stream(stream);
-    const uint64_t key_bytes = h_offsets ? h_offsets[n] : n * (uint64_t)key_stride;
-    const uint64_t off_bytes = h_offsets ? (n + 1) * 8 : 0, tab = ((uint64_t)num_filters + 1) * 8;
-    const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
-    const uint64_t o_kb = o_offs + adl_host::round_up(off_bytes, 256);
-    const uint64_t o_bo = o_kb + adl_host::round_up(tab, 256);
-    const uint64_t o_bm = o_bo + adl_host::round_up(tab, 256);
-    const uint64_t o_res = o_bm + adl_host::round_up(bm_bytes + 16, 256);
-    const uint64_t total = o_res + 256;
+    const uint64_t tab = ((uint64_t)num_filters + 1) * 8;
+    adl_host::StagePlan plan;
+    const adl_host::KeyBlock kb(plan, h_offsets, n, key_stride);
+    const uint64_t o_kb = plan.take(tab);
+    const uint64_t o_bo = plan.take(tab);
+    const uint64_t o_bm = plan.take(bm_bytes + 16);
+    const uint64_t o_res = plan.take(16);  // the end of the upload
     adl_host::Staging &sg = adl_host::t_stage;
-    if (int rc = sg.reserve(total, total)) return rc;
-    if (key_bytes) memcpy(sg.host, h_keys, key_bytes);
-    if (off_bytes) memcpy(sg.host + o_offs, h_offsets, off_bytes);
+    if (int rc = sg.reserve(plan.end, plan.end)) return rc;
+    kb.fill(sg.host, h_keys, h_offsets);
     memcpy(sg.host + o_kb, key_begin, tab);
     memcpy(sg.host + o_bo, h_bitmap_off, tab);
     if (bm_bytes) memcpy(sg.host + o_bm, h_bitmaps, bm_bytes);
     if (hipMemcpyAsync(sg.dev, sg.host, o_res, hipMemcpyHostToDevice, st) != hipSuccess) return ADL_ERR_DEVICE;
     uint64_t *d_res = reinterpret_cast<uint64_t *>(sg.dev + o_res);
-    int rc = verify_launch(sg.dev, h_offsets ? reinterpret_cast<uint64_t *>(sg.dev + o_offs) : nullptr, n, key_stride,
-                           reinterpret_cast<uint64_t *>(sg.dev + o_kb), num_filters, sg.dev + o_bm,
-                           reinterpret_cast<uint64_t *>(sg.dev + o_bo), nullptr, bits_per_key, d_res, st);
+    int rc = verify_launch(sg.dev, kb.offsets(sg.dev), n, key_stride, reinterpret_cast<uint64_t *>(sg.dev + o_kb),
+                           num_filters, sg.dev + o_bm, reinterpret_cast<uint64_t *>(sg.dev + o_bo), nullptr,
+                           bits_per_key, d_res, st);
     if (rc == ADL_OK && hipMemcpyAsync(sg.host + o_res, d_res, 16, hipMemcpyDeviceToHost, st) != hipSuccess)
       rc = ADL_ERR_DEVICE;
     if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;

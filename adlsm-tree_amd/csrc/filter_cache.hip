@@ -95,10 +95,6 @@ struct DoneEvent {
 };
 thread_local DoneEvent t_done;
 
-}  // namespace
-
-namespace {
-
 // What a probe resolved under the cache's lock: per listed table the arena
 // range of its filter (be[j], be[num_tables + j]), whether it is cached, its
 // block's k, and the entries it pinned.  (Per-thread scratch: a single-key
@@ -119,7 +115,7 @@ void resolve_tables(adl_bloom_filter_cache *c, const char *const *oids, const ui
   r.be.assign(2 * (size_t)num_tables, 0);
   r.cached.assign(num_tables, 0);
   r.kt.assign(num_tables, 1);
-  r.pinned.clear();
+  r.pinned.reserve(num_tables);  // (no entry is counted and then not listed)
   std::lock_guard<std::mutex> g(c->mu);
   for (uint32_t j = 0; j < num_tables; ++j) {
     r.oid_key.assign(oids[j], oid_lens[j]);
@@ -144,10 +140,57 @@ void resolve_tables(adl_bloom_filter_cache *c, const char *const *oids, const ui
   }
 }
 
-void unpin_tables(adl_bloom_filter_cache *c, Resolved &r) {
-  std::lock_guard<std::mutex> g(c->mu);
-  for (auto e : r.pinned) c->unpin(e);
+// Owns the pins resolve_tables takes into `r` (the thread's scratch: nothing
+// is allocated per call) and gives them back when it goes out of scope, on
+// every path (a range retired meanwhile is freed by its last unpin).  The
+// kernels and copies that read the pinned ranges must be complete by then, so
+// the scope of one ends after its call's last synchronize or watch_answers.
+class PinScope {
+ public:
+  PinScope(adl_bloom_filter_cache *c, Resolved &r) : c_(c), r_(r) { r_.pinned.clear(); }
+  PinScope(const PinScope &) = delete;
+  PinScope &operator=(const PinScope &) = delete;
+  ~PinScope() {
+    std::lock_guard<std::mutex> g(c_->mu);
+    for (auto e : r_.pinned) c_->unpin(e);
+    r_.pinned.clear();
+  }
+
+ private:
+  adl_bloom_filter_cache *c_;
+  Resolved &r_;
+};
+
+// resolve_tables on the tables of the given levels (null: an empty level), in
+// order, as one oid list of num_tables entries.
+void resolve_levels(adl_bloom_filter_cache *c, adl_bloom_level *const *levels, size_t num_levels, uint32_t num_tables,
+                    uint32_t filter, Resolved &r) {
+  std::vector<const char *> op;
+  std::vector<uint64_t> ol;
+  op.reserve(num_tables);
+  ol.reserve(num_tables);
+  for (size_t l = 0; l < num_levels; ++l) {
+    if (!levels[l]) continue;
+    for (const std::string &oid : levels[l]->oids) {
+      op.push_back(oid.data());
+      ol.push_back(oid.size());
+    }
+  }
+  resolve_tables(c, op.data(), ol.data(), num_tables, filter, r);
 }
+
+// The resolved tables' range table (begin[], then end[]) and k table, as every
+// cached probe stages them after its keys and ids.
+struct TableBlock {
+  uint64_t o_be, o_k;
+  TableBlock(adl_host::StagePlan &p, const Resolved &r) : o_be(p.take(r.be.size() * 8)), o_k(p.take(r.kt.size())) {}
+  void fill(uint8_t *hbuf, const Resolved &r) const {
+    memcpy(hbuf + o_be, r.be.data(), r.be.size() * 8);
+    if (!r.kt.empty()) memcpy(hbuf + o_k, r.kt.data(), r.kt.size());
+  }
+  const uint64_t *begin(const uint8_t *dbuf) const { return reinterpret_cast<const uint64_t *>(dbuf + o_be); }
+  const uint8_t *k(const uint8_t *dbuf) const { return dbuf + o_k; }
+};
 
 // Waits for a mapped small batch by watching its n answers arrive (each is
 // written once, 0 or 1, over a 0xFF sentinel, by the probe kernel's one store
@@ -176,6 +219,116 @@ bool watch_answers(const volatile uint8_t *ans, uint64_t n, hipEvent_t done, int
     if (late()) return false;
     __builtin_ia32_pause();
   }
+}
+
+// A single-key Get (up to adl_srv::kMaxQ queries) asks the cache's resident
+// server: no launch.  Its answers arrive, in h_out, after all its reads of the
+// pinned ranges.  adl_srv::kBusy: not served -- the batch is not eligible, the
+// server is switched off, missing or backing off, or no answer came in
+// adl_srv::kTimeout (a healthy GPU with no room for the server's wave) -- and
+// the caller probes by a launch, the ranges still pinned.
+int serve_resident(adl_bloom_filter_cache *c, const Resolved &res, uint32_t num_tables, const uint8_t *h_keys,
+                   const uint64_t *h_offsets, uint64_t n, uint32_t key_stride, const uint32_t *h_table,
+                   uint8_t *h_out) {
+  const uint64_t kbytes = h_offsets ? h_offsets[n] - h_offsets[0] : n * (uint64_t)key_stride;
+  if (!adl_srv::eligible(n, kbytes) || !adl_host::knobs().probe_server) return adl_srv::kBusy;
+  const int64_t now_ns =
+      std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  if (now_ns < c->srv_backoff_until.load(std::memory_order_relaxed)) return adl_srv::kBusy;
+  adl_srv::Server *srv = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->srv_tried) {
+      c->srv_tried = true;
+      c->srv = adl_srv::create();
+    }
+    srv = c->srv;
+  }
+  if (!srv) return adl_srv::kBusy;
+  uint64_t rng[2 * adl_srv::kMaxQ];
+  uint8_t kq[adl_srv::kMaxQ];
+  const uint64_t a0 = reinterpret_cast<uint64_t>(c->arena);
+  for (uint64_t i = 0; i < n; ++i) {
+    rng[2 * i] = a0 + res.be[h_table[i]];
+    rng[2 * i + 1] = a0 + res.be[num_tables + h_table[i]];
+    kq[i] = res.kt[h_table[i]];
+  }
+  int rc = adl_srv::probe(srv, h_keys, h_offsets, key_stride, n, rng, kq, c->epoch.load(std::memory_order_acquire),
+                          h_out);
+  if (rc == ADL_OK && adl_host::g_test_faults.take(ADL_TEST_FAULT_CACHE_COMPLETION) >= 0) rc = ADL_ERR_DEVICE;
+  if (rc == adl_srv::kBusy) c->srv_backoff_until.store(now_ns + kServerBackoffNs, std::memory_order_relaxed);
+  return rc;
+}
+
+// The body of a batch that answers a byte per query: the plan's sections up
+// to o_out are the upload, the n answers follow at o_out.  A small batch (a
+// single-key Get) is handed over in the thread's mapped buffer: the kernel
+// reads it and writes its answers there directly; a larger one is staged, sent
+// in one H2D and its answers fetched in one D2H.  fill(hbuf) places the
+// upload, launch(dbuf, done) enqueues the probe on `st`.
+//
+// A mapped small batch is waited for by watching its answers arrive (each is
+// written once, 0 or 1, over a 0xFF sentinel, by the probe kernel's one store
+// per query after all its reads) instead of a stream synchronize.  Its
+// completion event rides on the probe's dispatch packet, and the call returns
+// only once that has fired too, so a fault after the answers landed is still
+// this call's error.  Both waits fall back to the synchronize after 2 ms (or
+// with ADL_BLOOM_SPIN=0).  On return the kernel and the copies are done; the
+// answers are in h_out when the status is ADL_OK.
+template <class Fill, class Launch>
+int run_answer_batch(const adl_host::StagePlan &plan, uint64_t o_out, uint64_t n, hipStream_t st, Fill &&fill,
+                     Launch &&launch, uint8_t *h_out) {
+  adl_host::Staging &sg = adl_host::t_stage;
+  uint8_t *hbuf = adl_host::t_mapped.get(plan.end), *dbuf = adl_host::t_mapped.dev;
+  const bool mapped = hbuf != nullptr;
+  int rc = ADL_OK;
+  if (!mapped) {
+    rc = sg.reserve(plan.end, plan.end);
+    hbuf = sg.host;
+    dbuf = sg.dev;
+  }
+  const bool spin = mapped && n <= 4096 && adl_host::knobs().spin;
+  if (rc == ADL_OK) {
+    fill(hbuf);
+    if (spin) memset(hbuf + o_out, 0xff, n);
+    if (!mapped && hipMemcpyAsync(dbuf, hbuf, o_out, hipMemcpyHostToDevice, st) != hipSuccess) rc = ADL_ERR_DEVICE;
+  }
+  hipEvent_t done = spin && rc == ADL_OK ? t_done.get() : nullptr;
+  if (rc == ADL_OK) rc = launch(dbuf, done);
+  if (rc == ADL_OK && !mapped && hipMemcpyAsync(hbuf + o_out, dbuf + o_out, n, hipMemcpyDeviceToHost, st) != hipSuccess)
+    rc = ADL_ERR_DEVICE;
+  const bool finished = done && watch_answers(hbuf + o_out, n, done, rc);
+  if (!finished && hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
+  if (rc == ADL_OK) memcpy(h_out, hbuf + o_out, n);
+  return rc;
+}
+
+// The results of a multi-get, fetched from the thread's staging pair: the
+// area [o_counts, o_end) starts with the counts and what has a fixed size;
+// from o_payload on it holds lists whose lengths the counts give.  A small
+// area comes back in one copy; a larger one first learns the counts.
+// counted(piece) reads the counts from sg.host and names the list pieces they
+// call for, piece(at, bytes); it runs once the counts are in, whichever way
+// the area came.  rc: the status so far (the stream is synchronized whatever
+// it is).  On return the kernels and the copies are done.
+template <class Counted>
+int fetch_count_first(adl_host::Staging &sg, uint64_t o_counts, uint64_t o_payload, uint64_t o_end, hipStream_t st,
+                      int rc, Counted &&counted) {
+  const bool one_copy = o_end - o_counts <= (256u << 10);
+  if (rc == ADL_OK && hipMemcpyAsync(sg.host + o_counts, sg.dev + o_counts, (one_copy ? o_end : o_payload) - o_counts,
+                                     hipMemcpyDeviceToHost, st) != hipSuccess)
+    rc = ADL_ERR_DEVICE;
+  if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
+  if (rc != ADL_OK) return rc;
+  bool second = false;
+  counted([&](uint64_t at, uint64_t bytes) {
+    if (one_copy || !bytes) return;
+    second = true;
+    if (rc == ADL_OK && hipMemcpyAsync(sg.host + at, sg.dev + at, bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+      rc = ADL_ERR_DEVICE;
+  });
+  if (second && hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
+  return rc;
 }
 
 }  // namespace
@@ -316,113 +469,39 @@ int adl_bloom_filter_cache_probe(adl_bloom_filter_cache *c, const char *const *o
     for (uint64_t i = 0; i < n; ++i)
       if (h_table[i] >= num_tables) return ADL_ERR_INVALID_ARG;
     hipStream_t st = adl_host::sync_stream(stream);
-    // 1. under the lock: per listed table, the arena range of its filter
-    //    `filter` (the all-ones filter when the table is not cached, an empty
-    //    range when it has no such filter) and its block's k, its entry pinned
-    //    and marked used
+    // 1. under the lock: the listed tables' ranges and k, pinned and marked
+    //    used, until this call is done with them
     Resolved &res = t_res;
+    PinScope pins(c, res);
     resolve_tables(c, oids, oid_lens, num_tables, filter, res);
-    std::vector<uint64_t> &be = res.be;
-    std::vector<uint8_t> &cached = res.cached, &kt = res.kt;
-    auto unpin_all = [&] { unpin_tables(c, res); };
     uint64_t uncached = 0;
-    for (uint64_t i = 0; i < n; ++i) uncached += !cached[h_table[i]];
-    // A single-key Get (up to adl_srv::kMaxQ queries): the resident server,
-    // no launch.  Its answers arrive after all its reads of the pinned ranges.
-    {
-      const uint64_t kbytes = h_offsets ? h_offsets[n] - h_offsets[0] : n * (uint64_t)key_stride;
-      adl_srv::Server *srv = nullptr;
-      const int64_t now_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                 std::chrono::steady_clock::now().time_since_epoch())
-                                 .count();
-      if (adl_srv::eligible(n, kbytes) && adl_host::knobs().probe_server &&
-          now_ns >= c->srv_backoff_until.load(std::memory_order_relaxed)) {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (!c->srv_tried) {
-          c->srv_tried = true;
-          c->srv = adl_srv::create();
-        }
-        srv = c->srv;
-      }
-      if (srv) {
-        uint64_t rng[2 * adl_srv::kMaxQ];
-        uint8_t kq[adl_srv::kMaxQ];
-        const uint64_t a0 = reinterpret_cast<uint64_t>(c->arena);
-        for (uint64_t i = 0; i < n; ++i) {
-          rng[2 * i] = a0 + be[h_table[i]];
-          rng[2 * i + 1] = a0 + be[num_tables + h_table[i]];
-          kq[i] = kt[h_table[i]];
-        }
-        int rc = adl_srv::probe(srv, h_keys, h_offsets, key_stride, n, rng, kq,
-                                c->epoch.load(std::memory_order_acquire), h_out);
-        if (rc == ADL_OK && adl_host::g_test_faults.take(ADL_TEST_FAULT_CACHE_COMPLETION) >= 0) rc = ADL_ERR_DEVICE;
-        // kBusy: no answer in adl_srv::kTimeout (a healthy GPU with no room for
-        // the server's wave): probe by a launch below, the ranges still pinned
-        if (rc != adl_srv::kBusy) {
-          unpin_all();
-          if (rc) return rc;
-          if (h_uncached) *h_uncached = uncached;
-          return ADL_OK;
-        }
-        c->srv_backoff_until.store(now_ns + kServerBackoffNs, std::memory_order_relaxed);
-      }
+    for (uint64_t i = 0; i < n; ++i) uncached += !res.cached[h_table[i]];
+    // 2. a single-key Get: the resident server (its answer is in h_out when
+    //    this call returns, the pins given back on the way out)
+    int rc = serve_resident(c, res, num_tables, h_keys, h_offsets, n, key_stride, h_table, h_out);
+    if (rc == adl_srv::kBusy) {
+      // 3. without the lock: keys, offsets, table ids and the range and k
+      //    tables up, one probe launch, a byte per query down
+      adl_host::StagePlan plan;
+      const adl_host::KeyBlock kb(plan, h_offsets, n, key_stride);
+      const uint64_t o_fid = plan.take(n * 4);
+      const TableBlock tb(plan, res);
+      const uint64_t o_out = plan.take(n);
+      rc = run_answer_batch(
+          plan, o_out, n, st,
+          [&](uint8_t *hbuf) {
+            kb.fill(hbuf, h_keys, h_offsets);
+            memcpy(hbuf + o_fid, h_table, n * 4);
+            tb.fill(hbuf, res);
+          },
+          [&](uint8_t *dbuf, hipEvent_t done) {
+            return adl_host::adl_probe_ranges_device_ev(
+                dbuf, kb.offsets(dbuf), n, key_stride, reinterpret_cast<const uint32_t *>(dbuf + o_fid), num_tables,
+                c->arena, tb.begin(dbuf), tb.begin(dbuf) + num_tables, tb.k(dbuf), dbuf + o_out, st, done);
+          },
+          h_out);
     }
-    // 2. without the lock: stage keys, offsets, table ids and the range table
-    //    and the range and k tables in one H2D, one probe launch, one D2H
-    const uint64_t key_bytes = h_offsets ? h_offsets[n] : n * (uint64_t)key_stride;
-    const uint64_t off_bytes = h_offsets ? (n + 1) * 8 : 0;
-    const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
-    const uint64_t o_fid = o_offs + adl_host::round_up(off_bytes, 256);
-    const uint64_t o_be = o_fid + adl_host::round_up(n * 4, 256);
-    const uint64_t o_k = o_be + adl_host::round_up(be.size() * 8, 256);
-    const uint64_t o_out = o_k + adl_host::round_up(num_tables, 256);
-    const uint64_t total = o_out + adl_host::round_up(n, 256);
-    // A small batch (a single-key Get) is handed over in the thread's mapped
-    // buffer: the kernel reads it and writes its answers there directly.
-    adl_host::Staging &sg = adl_host::t_stage;
-    uint8_t *hbuf = adl_host::t_mapped.get(total), *dbuf = hbuf ? adl_host::t_mapped.dev : nullptr;
-    int rc = ADL_OK;
-    if (!hbuf) {
-      rc = sg.reserve(total, total);
-      hbuf = sg.host;
-      dbuf = sg.dev;
-    }
-    // A mapped small batch is waited for by watching its answers arrive (each
-    // is written once, 0 or 1, over a 0xFF sentinel, by bloom_probe_multi_kernel's
-    // one store per query after all its reads) instead of a stream
-    // synchronize.  The pinned ranges are released only once the launch's
-    // completion event has fired too, so a fault after the answers landed is
-    // still this call's error.  Both waits fall back to the synchronize after
-    // 2 ms (or with ADL_BLOOM_SPIN=0).
-    const bool spin = hbuf != sg.host && n <= 4096 && adl_host::knobs().spin;
-    if (rc == ADL_OK) {
-      if (key_bytes) memcpy(hbuf, h_keys, key_bytes);
-      if (off_bytes) memcpy(hbuf + o_offs, h_offsets, off_bytes);
-      memcpy(hbuf + o_fid, h_table, n * 4);
-      memcpy(hbuf + o_be, be.data(), be.size() * 8);
-      if (num_tables) memcpy(hbuf + o_k, kt.data(), num_tables);
-      if (spin) memset(hbuf + o_out, 0xff, n);
-      if (hbuf == sg.host && hipMemcpyAsync(dbuf, hbuf, o_out, hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = ADL_ERR_DEVICE;
-    }
-    // a watched batch's completion event rides on the probe's dispatch packet
-    hipEvent_t done = spin && rc == ADL_OK ? t_done.get() : nullptr;
-    if (rc == ADL_OK) {
-      const uint64_t *d_be = reinterpret_cast<const uint64_t *>(dbuf + o_be);
-      rc = adl_host::adl_probe_ranges_device_ev(dbuf, h_offsets ? reinterpret_cast<uint64_t *>(dbuf + o_offs) : nullptr, n,
-                                      key_stride, reinterpret_cast<const uint32_t *>(dbuf + o_fid), num_tables,
-                                      c->arena, d_be, d_be + num_tables, dbuf + o_k, dbuf + o_out, st, done);
-    }
-    if (rc == ADL_OK && hbuf == sg.host &&
-        hipMemcpyAsync(hbuf + o_out, dbuf + o_out, n, hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = ADL_ERR_DEVICE;
-    // the kernel and the copies are done before any pinned range can be reused
-    const bool finished = done && watch_answers(hbuf + o_out, n, done, rc);
-    if (!finished && hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
-    // 3. unpin (a range retired meanwhile is freed by its last unpin)
-    unpin_all();
     if (rc) return rc;
-    memcpy(h_out, hbuf + o_out, n);
     if (h_uncached) *h_uncached = uncached;
     return ADL_OK;
   } catch (...) {
@@ -449,8 +528,8 @@ int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *c, const char *c
     if (!h_pair_table || !h_out) return ADL_ERR_INVALID_ARG;
     for (uint64_t p = 0; p < np; ++p)
       if (h_pair_table[p] >= num_tables) return ADL_ERR_INVALID_ARG;
-    // A Get's worth of pairs: expanded, so that the small-batch path (the
-    // resident server, the mapped buffer) serves it as before.
+    // A Get's worth of pairs: expanded, so that adl_bloom_filter_cache_probe
+    // (the resident server) serves it as before.
     if (np <= adl_srv::kMaxQ) {
       std::string kbytes;
       uint64_t koff[adl_srv::kMaxQ + 1] = {0};
@@ -471,61 +550,35 @@ int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *c, const char *c
     hipStream_t st = adl_host::sync_stream(stream);
     // 1. under the lock: the listed tables' ranges and k, pinned and marked used
     Resolved &res = t_res;
+    PinScope pins(c, res);
     resolve_tables(c, oids, oid_lens, num_tables, filter, res);
     uint64_t uncached = 0;
     for (uint64_t p = 0; p < np; ++p) uncached += !res.cached[h_pair_table[p]];
     // 2. without the lock: keys (once each), their offsets, the begin array,
-    //    the table ids and the range and k tables in one H2D, one fan-out
-    //    launch, one D2H of a byte per pair
-    const uint64_t key_bytes = h_offsets ? h_offsets[num_keys] : num_keys * (uint64_t)key_stride;
-    const uint64_t off_bytes = h_offsets ? (num_keys + 1) * 8 : 0;
-    const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
-    const uint64_t o_pb = o_offs + adl_host::round_up(off_bytes, 256);
-    const uint64_t o_pt = o_pb + adl_host::round_up((num_keys + 1) * 4, 256);
-    const uint64_t o_be = o_pt + adl_host::round_up(np * 4, 256);
-    const uint64_t o_k = o_be + adl_host::round_up(res.be.size() * 8, 256);
-    const uint64_t o_out = o_k + adl_host::round_up(num_tables, 256);
-    const uint64_t total = o_out + adl_host::round_up(np, 256);
-    // a small batch goes through the thread's mapped buffer and is waited for
-    // by watching its answers, as in adl_bloom_filter_cache_probe
-    adl_host::Staging &sg = adl_host::t_stage;
-    uint8_t *hbuf = adl_host::t_mapped.get(total), *dbuf = hbuf ? adl_host::t_mapped.dev : nullptr;
-    int rc = ADL_OK;
-    if (!hbuf) {
-      rc = sg.reserve(total, total);
-      hbuf = sg.host;
-      dbuf = sg.dev;
-    }
-    const bool spin = hbuf != sg.host && np <= 4096 && adl_host::knobs().spin;
-    if (rc == ADL_OK) {
-      if (key_bytes) memcpy(hbuf, h_keys, key_bytes);
-      if (off_bytes) memcpy(hbuf + o_offs, h_offsets, off_bytes);
-      memcpy(hbuf + o_pb, h_pair_begin, (num_keys + 1) * 4);
-      memcpy(hbuf + o_pt, h_pair_table, np * 4);
-      memcpy(hbuf + o_be, res.be.data(), res.be.size() * 8);
-      memcpy(hbuf + o_k, res.kt.data(), num_tables);
-      if (spin) memset(hbuf + o_out, 0xff, np);
-      if (hbuf == sg.host && hipMemcpyAsync(dbuf, hbuf, o_out, hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = ADL_ERR_DEVICE;
-    }
-    hipEvent_t done = spin && rc == ADL_OK ? t_done.get() : nullptr;
-    if (rc == ADL_OK) {
-      const uint64_t *d_be = reinterpret_cast<const uint64_t *>(dbuf + o_be);
-      rc = adl_host::adl_probe_fanout_device_ev(
-          dbuf, h_offsets ? reinterpret_cast<uint64_t *>(dbuf + o_offs) : nullptr, num_keys, key_stride,
-          reinterpret_cast<const uint32_t *>(dbuf + o_pb), reinterpret_cast<const uint32_t *>(dbuf + o_pt), np,
-          num_tables, c->arena, d_be, d_be + num_tables, dbuf + o_k, dbuf + o_out, st, done);
-    }
-    if (rc == ADL_OK && hbuf == sg.host &&
-        hipMemcpyAsync(hbuf + o_out, dbuf + o_out, np, hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = ADL_ERR_DEVICE;
-    // the kernel and the copies are done before any pinned range can be reused
-    const bool finished = done && watch_answers(hbuf + o_out, np, done, rc);
-    if (!finished && hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
-    // 3. unpin (a range retired meanwhile is freed by its last unpin)
-    unpin_tables(c, res);
+    //    the table ids and the range and k tables up, one fan-out launch, a
+    //    byte per pair down
+    adl_host::StagePlan plan;
+    const adl_host::KeyBlock kb(plan, h_offsets, num_keys, key_stride);
+    const uint64_t o_pb = plan.take((num_keys + 1) * 4);
+    const uint64_t o_pt = plan.take(np * 4);
+    const TableBlock tb(plan, res);
+    const uint64_t o_out = plan.take(np);
+    const int rc = run_answer_batch(
+        plan, o_out, np, st,
+        [&](uint8_t *hbuf) {
+          kb.fill(hbuf, h_keys, h_offsets);
+          memcpy(hbuf + o_pb, h_pair_begin, (num_keys + 1) * 4);
+          memcpy(hbuf + o_pt, h_pair_table, np * 4);
+          tb.fill(hbuf, res);
+        },
+        [&](uint8_t *dbuf, hipEvent_t done) {
+          return adl_host::adl_probe_fanout_device_ev(
+              dbuf, kb.offsets(dbuf), num_keys, key_stride, reinterpret_cast<const uint32_t *>(dbuf + o_pb),
+              reinterpret_cast<const uint32_t *>(dbuf + o_pt), np, num_tables, c->arena, tb.begin(dbuf),
+              tb.begin(dbuf) + num_tables, tb.k(dbuf), dbuf + o_out, st, done);
+        },
+        h_out);
     if (rc) return rc;
-    memcpy(h_out, hbuf + o_out, np);
     if (h_uncached) *h_uncached = uncached;
     return ADL_OK;
   } catch (...) {
@@ -557,84 +610,57 @@ int adl_bloom_level_multiget(adl_bloom_level *lv, adl_bloom_filter_cache *c, uin
     const uint64_t cap = std::min<uint64_t>(pair_capacity, 0xffffffffull);
     // 1. under the lock: the level's tables' ranges and k, pinned and marked used
     Resolved &res = t_res;
-    {
-      std::vector<const char *> op(num_tables);
-      std::vector<uint64_t> ol(num_tables);
-      for (uint32_t t = 0; t < num_tables; ++t) {
-        op[t] = lv->oids[t].data();
-        ol[t] = lv->oids[t].size();
-      }
-      resolve_tables(c, op.data(), ol.data(), num_tables, filter, res);
-    }
+    PinScope pins(c, res);
+    resolve_levels(c, &lv, 1, num_tables, filter, res);
     // 2. without the lock: keys, offsets and the range and k tables in one H2D;
-    //    selection (three launches) and the fan-out probe; then the results
-    const uint64_t key_bytes = h_offsets ? h_offsets[num_keys] : num_keys * (uint64_t)key_stride;
-    const uint64_t off_bytes = h_offsets ? (num_keys + 1) * 8 : 0;
+    //    selection (three launches) and the fan-out probe; then the results:
+    //    num_pairs, the begin array | the table ids and answers | scratch
     const uint64_t wsb = adl_bloom_level_candidates_workspace_bytes(num_keys);
-    const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
-    const uint64_t o_be = o_offs + adl_host::round_up(off_bytes, 256);
-    const uint64_t o_k = o_be + adl_host::round_up(res.be.size() * 8, 256);
-    const uint64_t o_np = o_k + adl_host::round_up(num_tables, 256);  // end of the upload
-    const uint64_t o_pb = o_np + 256;
-    const uint64_t o_pt = o_pb + adl_host::round_up((num_keys + 1) * 4, 256);
-    const uint64_t o_out = o_pt + adl_host::round_up(cap * 4, 256);
-    const uint64_t o_ws = o_out + adl_host::round_up(cap, 256);
-    const uint64_t total = o_ws + wsb;
+    adl_host::StagePlan plan;
+    const adl_host::KeyBlock kb(plan, h_offsets, num_keys, key_stride);
+    const TableBlock tb(plan, res);
+    const uint64_t o_np = plan.take(8);  // the end of the upload
+    const uint64_t o_pb = plan.take((num_keys + 1) * 4);
+    const uint64_t o_pt = plan.take(cap * 4);
+    const uint64_t o_out = plan.take(cap);
+    const uint64_t o_ws = plan.take(wsb);  // the end of what the host buffer holds
     adl_host::Staging &sg = adl_host::t_stage;
-    int rc = sg.reserve(o_ws, total);
+    int rc = sg.reserve(o_ws, plan.end);
     uint8_t *hbuf = sg.host, *dbuf = sg.dev;
-    uint64_t np = 0;
     if (rc == ADL_OK) {
-      if (key_bytes) memcpy(hbuf, h_keys, key_bytes);
-      if (off_bytes) memcpy(hbuf + o_offs, h_offsets, off_bytes);
-      memcpy(hbuf + o_be, res.be.data(), res.be.size() * 8);
-      if (num_tables) memcpy(hbuf + o_k, res.kt.data(), num_tables);
+      kb.fill(hbuf, h_keys, h_offsets);
+      tb.fill(hbuf, res);
       if (hipMemcpyAsync(dbuf, hbuf, o_np, hipMemcpyHostToDevice, st) != hipSuccess) rc = ADL_ERR_DEVICE;
     }
-    const uint64_t *d_offs = h_offsets ? reinterpret_cast<const uint64_t *>(dbuf + o_offs) : nullptr;
     uint32_t *d_pb = reinterpret_cast<uint32_t *>(dbuf + o_pb), *d_pt = reinterpret_cast<uint32_t *>(dbuf + o_pt);
     if (rc == ADL_OK)
-      rc = adl_host::level_select_device(lv, dbuf, d_offs, num_keys, key_stride, seq, d_pb, d_pt, cap,
+      rc = adl_host::level_select_device(lv, dbuf, kb.offsets(dbuf), num_keys, key_stride, seq, d_pb, d_pt, cap,
                                          reinterpret_cast<uint64_t *>(dbuf + o_np), dbuf + o_ws, wsb, st);
-    if (rc == ADL_OK && cap) {
-      // (the kernel stops at cap pairs whatever pair_begin says)
-      const uint64_t *d_be = reinterpret_cast<const uint64_t *>(dbuf + o_be);
-      rc = adl_host::adl_probe_fanout_device_ev(dbuf, d_offs, num_keys, key_stride, d_pb, d_pt, cap, num_tables,
-                                                c->arena, d_be, d_be + num_tables, dbuf + o_k, dbuf + o_out, st,
-                                                nullptr);
-    }
-    // A batch whose whole result area is small comes back in one copy; a
-    // larger one first learns how many pairs there are.
-    const bool one_copy = o_ws - o_np <= (256u << 10);
-    if (rc == ADL_OK &&
-        hipMemcpyAsync(hbuf + o_np, dbuf + o_np, one_copy ? o_ws - o_np : o_pt - o_np, hipMemcpyDeviceToHost, st) !=
-            hipSuccess)
-      rc = ADL_ERR_DEVICE;
-    if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
-    if (rc == ADL_OK) {
+    if (rc == ADL_OK && cap)  // (the kernel stops at cap pairs whatever pair_begin says)
+      rc = adl_host::adl_probe_fanout_device_ev(dbuf, kb.offsets(dbuf), num_keys, key_stride, d_pb, d_pt, cap,
+                                                num_tables, c->arena, tb.begin(dbuf), tb.begin(dbuf) + num_tables,
+                                                tb.k(dbuf), dbuf + o_out, st, nullptr);
+    uint64_t np = 0;
+    rc = fetch_count_first(sg, o_np, o_pt, o_ws, st, rc, [&](auto piece) {
       memcpy(&np, hbuf + o_np, 8);
       const uint64_t have = std::min(np, cap);
-      if (!one_copy && have) {
-        if (hipMemcpyAsync(hbuf + o_pt, dbuf + o_pt, have * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(hbuf + o_out, dbuf + o_out, have, hipMemcpyDeviceToHost, st) != hipSuccess)
-          rc = ADL_ERR_DEVICE;
-        if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
-      }
-    }
-    // 3. the kernels and the copies are done: unpin
-    uint64_t uncached = 0;
-    if (rc == ADL_OK && np <= cap) {
-      const uint32_t *pt = reinterpret_cast<const uint32_t *>(hbuf + o_pt);
-      for (uint64_t p = 0; p < np; ++p) uncached += !res.cached[pt[p]];
-    }
-    unpin_tables(c, res);
+      piece(o_pt, have * 4);
+      piece(o_out, have);
+    });
+    // 3. the kernels and the copies are done: report (the uncached pairs are
+    //    counted where the ids arrived, before anything is copied out: a large
+    //    copy leaves neither side in the CPU's caches)
     if (rc) return rc;
+    uint64_t uncached = 0;
+    const uint32_t *pt = reinterpret_cast<const uint32_t *>(hbuf + o_pt);
+    if (np <= cap)
+      for (uint64_t p = 0; p < np; ++p) uncached += !res.cached[pt[p]];
     *num_pairs = np;
     if (np > 0xffffffffull) return ADL_ERR_TOO_LARGE;
     memcpy(h_pair_begin, hbuf + o_pb, (num_keys + 1) * 4);
     if (np > pair_capacity) return ADL_ERR_WORKSPACE;
     if (np) {
-      memcpy(h_pair_table, hbuf + o_pt, np * 4);
+      memcpy(h_pair_table, pt, np * 4);
       memcpy(h_out, hbuf + o_out, np);
     }
     if (h_uncached) *h_uncached = uncached;
@@ -674,94 +700,62 @@ int adl_bloom_revision_multiget(adl_bloom_revision *rev, adl_bloom_filter_cache 
     const uint64_t hcap = std::min(hit_capacity, cap);  // (no more hits than pairs)
     // 1. under the lock: every level's tables' ranges and k, pinned and marked used
     Resolved &res = t_res;
-    {
-      std::vector<const char *> op;
-      std::vector<uint64_t> ol;
-      op.reserve(num_tables);
-      ol.reserve(num_tables);
-      for (adl_bloom_level *lv : rev->levels) {
-        if (!lv) continue;
-        for (uint32_t t = 0; t < lv->ix.num_tables; ++t) {
-          op.push_back(lv->oids[t].data());
-          ol.push_back(lv->oids[t].size());
-        }
-      }
-      resolve_tables(c, op.data(), ol.data(), num_tables, filter, res);
-    }
+    PinScope pins(c, res);
+    resolve_levels(c, rev->levels.data(), rev->levels.size(), num_tables, filter, res);
     // 2. without the lock: keys, offsets and the range and k tables in one H2D;
-    //    selection (three launches), probe + hit count, scan, compaction
-    const uint64_t key_bytes = h_offsets ? h_offsets[num_keys] : num_keys * (uint64_t)key_stride;
-    const uint64_t off_bytes = h_offsets ? (num_keys + 1) * 8 : 0;
+    //    selection (three launches), probe + hit count, scan, compaction; then
+    //    the results: num_pairs and num_hits, the hit begin array | the hits |
+    //    the candidate pairs and scratch, on the device only
     const uint64_t wsc = adl_bloom_revision_candidates_workspace_bytes(rev, num_keys);
     const uint64_t wsh = adl_bloom_probe_fanout_hits_workspace_bytes(num_keys, cap);
-    const uint64_t o_offs = adl_host::round_up(key_bytes + 16, 256);
-    const uint64_t o_be = o_offs + adl_host::round_up(off_bytes, 256);
-    const uint64_t o_k = o_be + adl_host::round_up(res.be.size() * 8, 256);
-    const uint64_t o_np = o_k + adl_host::round_up(num_tables, 256);  // end of the upload: num_pairs, num_hits
-    const uint64_t o_hb = o_np + 256;
-    const uint64_t o_ht = o_hb + adl_host::round_up((num_keys + 1) * 4, 256);
-    const uint64_t o_pb = o_ht + adl_host::round_up(hcap * 4, 256);  // end of what comes back
-    const uint64_t o_pt = o_pb + adl_host::round_up((num_keys + 1) * 4, 256);
-    const uint64_t o_wsc = o_pt + adl_host::round_up(cap * 4, 256);
-    const uint64_t o_wsh = o_wsc + wsc;
-    const uint64_t total = o_wsh + wsh;
+    adl_host::StagePlan plan;
+    const adl_host::KeyBlock kb(plan, h_offsets, num_keys, key_stride);
+    const TableBlock tb(plan, res);
+    const uint64_t o_np = plan.take(16);  // the end of the upload: num_pairs, num_hits
+    const uint64_t o_hb = plan.take((num_keys + 1) * 4);
+    const uint64_t o_ht = plan.take(hcap * 4);
+    const uint64_t o_pb = plan.take((num_keys + 1) * 4);  // the end of what comes back
+    const uint64_t o_pt = plan.take(cap * 4);
+    const uint64_t o_wsc = plan.take(wsc);
+    const uint64_t o_wsh = plan.take(wsh);
     adl_host::Staging &sg = adl_host::t_stage;
-    int rc = sg.reserve(o_pb, total);
+    int rc = sg.reserve(o_pb, plan.end);
     uint8_t *hbuf = sg.host, *dbuf = sg.dev;
     if (rc == ADL_OK) {
-      if (key_bytes) memcpy(hbuf, h_keys, key_bytes);
-      if (off_bytes) memcpy(hbuf + o_offs, h_offsets, off_bytes);
-      memcpy(hbuf + o_be, res.be.data(), res.be.size() * 8);
-      if (num_tables) memcpy(hbuf + o_k, res.kt.data(), num_tables);
+      kb.fill(hbuf, h_keys, h_offsets);
+      tb.fill(hbuf, res);
       if (hipMemcpyAsync(dbuf, hbuf, o_np, hipMemcpyHostToDevice, st) != hipSuccess) rc = ADL_ERR_DEVICE;
     }
-    const uint64_t *d_offs = h_offsets ? reinterpret_cast<const uint64_t *>(dbuf + o_offs) : nullptr;
     uint32_t *d_pb = reinterpret_cast<uint32_t *>(dbuf + o_pb), *d_pt = reinterpret_cast<uint32_t *>(dbuf + o_pt);
     if (rc == ADL_OK)
-      rc = adl_host::revision_select_device(rev, dbuf, d_offs, num_keys, key_stride, seq, d_pb, d_pt, cap,
+      rc = adl_host::revision_select_device(rev, dbuf, kb.offsets(dbuf), num_keys, key_stride, seq, d_pb, d_pt, cap,
                                             reinterpret_cast<uint64_t *>(dbuf + o_np), dbuf + o_wsc, wsc, st);
-    if (rc == ADL_OK) {
-      // (the kernels stop at cap pairs whatever pair_begin says)
-      const uint64_t *d_be = reinterpret_cast<const uint64_t *>(dbuf + o_be);
-      rc = adl_host::probe_fanout_hits_device(dbuf, d_offs, num_keys, key_stride, d_pb, d_pt, cap, num_tables,
-                                              c->arena, d_be, d_be + num_tables, 10, dbuf + o_k,
-                                              reinterpret_cast<uint32_t *>(dbuf + o_hb),
+    if (rc == ADL_OK)  // (the kernels stop at cap pairs whatever pair_begin says)
+      rc = adl_host::probe_fanout_hits_device(dbuf, kb.offsets(dbuf), num_keys, key_stride, d_pb, d_pt, cap,
+                                              num_tables, c->arena, tb.begin(dbuf), tb.begin(dbuf) + num_tables, 10,
+                                              tb.k(dbuf), reinterpret_cast<uint32_t *>(dbuf + o_hb),
                                               reinterpret_cast<uint32_t *>(dbuf + o_ht), hcap,
                                               reinterpret_cast<uint64_t *>(dbuf + o_np + 8), dbuf + o_wsh, wsh, st);
-    }
-    // A batch whose whole result area is small comes back in one copy; a
-    // larger one first learns how many hits there are.
-    const bool one_copy = o_pb - o_np <= (256u << 10);
-    if (rc == ADL_OK &&
-        hipMemcpyAsync(hbuf + o_np, dbuf + o_np, one_copy ? o_pb - o_np : o_ht - o_np, hipMemcpyDeviceToHost, st) !=
-            hipSuccess)
-      rc = ADL_ERR_DEVICE;
-    if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
     uint64_t np = 0, nh = 0;
-    if (rc == ADL_OK) {
+    rc = fetch_count_first(sg, o_np, o_ht, o_pb, st, rc, [&](auto piece) {
       memcpy(&np, hbuf + o_np, 8);
       memcpy(&nh, hbuf + o_np + 8, 8);
-      if (!one_copy && np <= cap && nh && nh <= hcap) {
-        if (hipMemcpyAsync(hbuf + o_ht, dbuf + o_ht, nh * 4, hipMemcpyDeviceToHost, st) != hipSuccess)
-          rc = ADL_ERR_DEVICE;
-        if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
-      }
-    }
-    // 3. the kernels and the copies are done: unpin
-    uint64_t uncached = 0;
-    if (rc == ADL_OK && np <= cap && nh <= hcap) {
-      const uint32_t *ht = reinterpret_cast<const uint32_t *>(hbuf + o_ht);
-      for (uint64_t p = 0; p < nh; ++p) uncached += !res.cached[ht[p]];
-    }
-    unpin_tables(c, res);
+      if (np <= cap && nh <= hcap) piece(o_ht, nh * 4);
+    });
+    // 3. the kernels and the copies are done: report (the uncached hits are
+    //    counted where the ids arrived, before anything is copied out)
     if (rc) return rc;
+    uint64_t uncached = 0;
+    const uint32_t *ht = reinterpret_cast<const uint32_t *>(hbuf + o_ht);
+    if (np <= cap && nh <= hcap)
+      for (uint64_t p = 0; p < nh; ++p) uncached += !res.cached[ht[p]];
     *num_pairs = np;
     if (np > 0xffffffffull) return ADL_ERR_TOO_LARGE;
     if (np > cap) return ADL_ERR_WORKSPACE;  // (the hits of the first cap pairs only: nothing else is reported)
     *num_hits = nh;
     memcpy(h_hit_begin, hbuf + o_hb, (num_keys + 1) * 4);
     if (nh > hit_capacity) return ADL_ERR_WORKSPACE;
-    if (nh) memcpy(h_hit_table, hbuf + o_ht, nh * 4);
+    if (nh) memcpy(h_hit_table, ht, nh * 4);
     if (h_uncached) *h_uncached = uncached;
     return ADL_OK;
   } catch (...) {

@@ -6,7 +6,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <numeric>
 
 #include "adl_bloom.h"
 #include "level_index_core.hpp"
@@ -46,152 +45,39 @@ void LevelCandidates(const vector<TableRange> &tables, const vector<string_view>
   const size_t K = user_keys.size(), T = tables.size();
   begin.assign(K + 1, 0);
   table.clear();
-  // The per-call form of the region index: sorted, swept and searched for this
-  // one batch at this one seq.  A caller that asks about the same level again
-  // keeps a LevelIndex (level_index_core.hpp), which builds the same regions
-  // once, independent of seq.
-  // files_meta_ order (ascending min_inner_key, stable), visited in reverse
-  vector<uint32_t> asc(T);
-  std::iota(asc.begin(), asc.end(), 0u);
-  std::stable_sort(asc.begin(), asc.end(), [&](uint32_t a, uint32_t b) {
-    return InnerKeyLess(tables[a].min_inner_key, tables[b].min_inner_key);
-  });
-  vector<Decoded> mn(T), mx(T);
+  // The per-call form of a LevelIndex: the region index (level_index_core.hpp)
+  // built for this one batch and looked up once.  A caller that asks about the
+  // same level again keeps a LevelIndex instead.
+  vector<string_view> mins(T), maxs(T);
   for (size_t t = 0; t < T; ++t) {
-    mn[t] = Decode(tables[t].min_inner_key);
-    mx[t] = Decode(tables[t].max_inner_key);
+    mins[t] = tables[t].min_inner_key;
+    maxs[t] = tables[t].max_inner_key;
   }
-  // Table t is a candidate for lookup mk = (u, seq, OP_PUT) (src/revision.cpp:
-  // 281-287) iff mn[t].user <= u and !(mx[t] < mk): with seq fixed for the
-  // batch, that is u in [mn.user, mx.user), plus u == mx.user unless
-  // gone_at_max[t] = (mx[t] < (mx.user, seq, OP_PUT)).  So the candidate list
-  // is constant on each region the tables' boundary user keys B cut the key
-  // space into (a gap between two of them, or one of them).  One sweep over B
-  // builds every region's list in Level::Get's visiting order -- a table enters
-  // at the front of the active list (ascending min order, so the list stays in
-  // visiting order) and leaves at its max -- and a lookup is a binary search
-  // in B plus a copy: O(K log T + candidates), no K x T range tests.
-  vector<string_view> B;
-  B.reserve(2 * T);
-  for (size_t t = 0; t < T; ++t) {
-    B.push_back(mn[t].user);
-    B.push_back(mx[t].user);
-  }
-  std::sort(B.begin(), B.end());
-  B.erase(std::unique(B.begin(), B.end()), B.end());
-  const size_t NB = B.size();
-  // lookups compare a 16-byte big-endian prefix first (two u64 compares), the
-  // whole keys only on a tie
-  struct Pref {
-    uint64_t hi, lo;
-  };
-  auto pref = [](string_view u) {
-    uint64_t w[2] = {0, 0};
-    memcpy(w, u.data(), u.size() < 16 ? u.size() : 16);
-    return Pref{__builtin_bswap64(w[0]), __builtin_bswap64(w[1])};
-  };
-  vector<Pref> bp(NB);
-  for (size_t i = 0; i < NB; ++i) bp[i] = pref(B[i]);
-  auto less_b = [&](size_t i, const Pref &p, string_view u) {  // B[i] < u
-    if (bp[i].hi != p.hi) return bp[i].hi < p.hi;
-    if (bp[i].lo != p.lo) return bp[i].lo < p.lo;
-    return B[i] < u;
-  };
-  auto at_p = [&](const Pref &p, string_view u) {  // lower_bound
-    size_t lo = 0, n = NB;
-    while (n) {
-      const size_t h = n / 2;
-      if (less_b(lo + h, p, u)) {
-        lo += h + 1;
-        n -= h + 1;
-      } else {
-        n = h;
-      }
-    }
-    return (uint32_t)lo;
-  };
-  auto at = [&](string_view u) { return at_p(pref(u), u); };
-  vector<vector<uint32_t>> ins(NB), out_pt(NB), out_gap(NB);  // per boundary: enter, leave before / after it
-  // a table whose max user key sorts before its min (no real table) is never a candidate
-  vector<uint8_t> never(T, 0);
-  for (size_t t = 0; t < T; ++t) never[t] = mx[t].user < mn[t].user;
-  for (uint32_t t : asc)
-    if (!never[t]) ins[at(mn[t].user)].push_back(t);
-  for (size_t t = 0; t < T; ++t) {
-    if (never[t]) continue;
-    const bool gone_at_max = Less(mx[t], Decoded{mx[t].user, seq, 0});
-    (gone_at_max ? out_pt : out_gap)[at(mx[t].user)].push_back((uint32_t)t);
-  }
-  vector<uint8_t> gone(T, 0);
-  for (size_t t = 0; t < T; ++t) gone[t] = !never[t] && Less(mx[t], Decoded{mx[t].user, seq, 0});
+  adl_level::Index ix;
+  adl_level::Sweep sw;
   // The region lists hold sum(active tables per region) entries: for heavily
   // overlapping tables (L0, wide ranges) that is O(T^2) whatever K is.  When it
-  // would exceed the K x T range tests of a direct scan, scan directly (the
-  // same predicate, in the same visiting order).
-  uint64_t total = 0;
-  {
-    int64_t active = 0;
-    for (size_t i = 0; i < NB; ++i) {
-      total += (uint64_t)active;  // the gap before B[i]
-      active += (int64_t)ins[i].size() - (int64_t)out_pt[i].size();
-      total += (uint64_t)active;  // B[i]
-      active -= (int64_t)out_gap[i].size();
-    }
-    total += (uint64_t)active;
-  }
-  if (total > (uint64_t)K * T) {
-    auto covers = [&](uint32_t t, string_view u) {
-      if (never[t] || u < mn[t].user) return false;
-      return u < mx[t].user || (u == mx[t].user && !gone[t]);
-    };
+  // would exceed the K x T range tests of a direct scan (or the index's
+  // limits), scan directly: the same predicate, in the same visiting order,
+  // decided before any list is built.  The index lists a table at its own max
+  // boundary even where this seq drops it there, so the count can be up to T
+  // entries above what this one lookup needs and a borderline level may take
+  // the other algorithm; the output is the same either way.
+  if (!adl_level::Prepare(mins.data(), maxs.data(), T, ix, sw) || sw.total > (uint64_t)K * T ||
+      !adl_level::Finish(sw, ~0ull, ix)) {
     for (size_t i = 0; i < K; ++i) {
-      for (size_t r = T; r-- > 0;)
-        if (covers(asc[r], user_keys[i])) table.push_back(asc[r]);
+      const string_view u = user_keys[i];
+      for (size_t r = T; r-- > 0;) {
+        const uint32_t t = sw.asc[r];
+        const Decoded &mn = sw.mn[t], &mx = sw.mx[t];
+        if (sw.never(t) || u < mn.user) continue;
+        if (u < mx.user || (u == mx.user && !Less(mx, Decoded{mx.user, seq, 0}))) table.push_back(t);
+      }
       begin[i + 1] = (uint32_t)table.size();
     }
     return;
   }
-  // region r: 2i = the gap before B[i], 2i+1 = B[i], 2*NB = the gap after the last
-  vector<uint64_t> rbeg(2 * NB + 2, 0);
-  vector<uint32_t> rlist;
-  rlist.reserve(total);
-  constexpr uint32_t kNil = ~0u;
-  vector<uint32_t> nxt(T, kNil), prv(T, kNil);
-  uint32_t head = kNil;
-  auto unlink = [&](uint32_t t) {
-    if (prv[t] != kNil) nxt[prv[t]] = nxt[t];
-    else head = nxt[t];
-    if (nxt[t] != kNil) prv[nxt[t]] = prv[t];
-  };
-  auto record = [&](size_t r) {
-    for (uint32_t t = head; t != kNil; t = nxt[t]) rlist.push_back(t);
-    rbeg[r + 1] = rlist.size();
-  };
-  for (size_t i = 0; i < NB; ++i) {
-    record(2 * i);  // the gap before B[i]
-    for (uint32_t t : ins[i]) {
-      nxt[t] = head;
-      prv[t] = kNil;
-      if (head != kNil) prv[head] = t;
-      head = t;
-    }
-    for (uint32_t t : out_pt[i]) unlink(t);
-    record(2 * i + 1);
-    for (uint32_t t : out_gap[i]) unlink(t);
-  }
-  record(2 * NB);
-  // each key's region, then the lists copied out in one pass
-  vector<uint32_t> reg(K);
-  for (size_t i = 0; i < K; ++i) {
-    const string_view u = user_keys[i];
-    const uint32_t j = at(u);
-    const uint32_t r = (j < NB && B[j] == u) ? 2 * j + 1 : 2 * j;
-    reg[i] = r;
-    begin[i + 1] = begin[i] + (rbeg[r + 1] - rbeg[r]);
-  }
-  table.resize(begin[K]);
-  for (size_t i = 0; i < K; ++i)
-    std::copy(rlist.begin() + rbeg[reg[i]], rlist.begin() + rbeg[reg[i] + 1], table.begin() + begin[i]);
+  adl_level::Lookup(ix, K, [&](size_t i) { return user_keys[i]; }, seq, begin.data(), table);
 }
 
 namespace {
@@ -266,6 +152,39 @@ RC FromStatus(int status) {
   return DEVICE_ERROR;
 }
 
+size_t KeyBytes(const vector<string_view> &user_keys) {
+  size_t bytes = 0;
+  for (string_view k : user_keys) bytes += k.size();
+  return bytes;
+}
+
+/* The batch's keys, each once, packed into `batch` for upload (key_bytes = KeyBytes(user_keys)). */
+void PackKeys(const vector<string_view> &user_keys, size_t key_bytes, KeyArena &batch) {
+  batch.Reserve(user_keys.size(), key_bytes);
+  for (string_view k : user_keys) batch.Add(k);
+}
+
+/* The result capacities of a device multi-get.  No key has more candidates
+ * than its level's longest list, but one wide region must not size every
+ * batch's buffers (here and, pinned, in the library) for K x longest: `first`,
+ * room for twice the mean list per key, and then the exact size, which the
+ * call reports (ADL_ERR_WORKSPACE with np > pcap or nh > hcap), where a batch
+ * needs more -- never beyond `worst`.  call(pcap, hcap) makes the call with
+ * those pair and hit capacities and sets np and nh; returns its last status. */
+template <class Call>
+int CallWithGrownCapacity(uint64_t first, uint64_t worst, uint64_t &np, uint64_t &nh, Call &&call) {
+  uint64_t pcap = std::min(worst, first), hcap = pcap;
+  int st = ADL_OK;
+  for (int attempt = 0; attempt < 3; ++attempt) {
+    st = call(pcap, hcap);
+    if (st != ADL_ERR_WORKSPACE || np > worst) break;
+    if (np > pcap) pcap = np;
+    else if (nh > hcap) hcap = nh;
+    else break;
+  }
+  return st;
+}
+
 /* The probes of a selected batch: out.begin / out.table are key i's candidates;
  * fills out.maybe and out.uncached. */
 RC ProbeSelected(FilterCache &cache, const vector<string_view> &oids, const vector<string_view> &user_keys,
@@ -286,8 +205,7 @@ RC ProbeSelected(FilterCache &cache, const vector<string_view> &oids, const vect
   if (mode >= 2 || (mode == 1 && saved >= kFanoutMinSavedBytes)) {
     // each key once, probed against its candidate list (out.begin / out.table
     // as they are): uploaded and hashed once per key instead of once per pair
-    batch.Reserve(K, key_bytes);
-    for (string_view k : user_keys) batch.Add(k);
+    PackKeys(user_keys, key_bytes, batch);
     return cache.ProbeFanout(oids, out.begin, out.table, batch, 0, out.maybe, &out.uncached);
   }
   // the probe batch: pair p = (key, table)
@@ -382,29 +300,18 @@ RC LevelMultiGetFilter(FilterCache &cache, LevelIndex &level, const vector<strin
   if (!cache.handle()) return cache.status();
   // keys up, lists and answers down: selection, expansion and the probes on
   // the device.
-  size_t key_bytes = 0;
-  for (string_view k : user_keys) key_bytes += k.size();
   KeyArena batch;
-  batch.Reserve(K, key_bytes);
-  for (string_view k : user_keys) batch.Add(k);
-  // No key has more than longest_list() candidates, but one wide region must
-  // not size every batch's buffers (here and, pinned, in the library) for
-  // K x longest: room for twice the mean list per key first, and the exact
-  // size, which the call reports, where a batch needs more.
+  PackKeys(user_keys, KeyBytes(user_keys), batch);
   const uint64_t worst = std::min<uint64_t>((uint64_t)K * level.longest_list(), 0xffffffffull);
-  uint64_t cap = std::min<uint64_t>(worst, 2ull * K * level.mean_list() + 1024);
   out.begin.assign(K + 1, 0);
-  uint64_t np = 0;
-  int st = ADL_OK;
-  for (int attempt = 0; attempt < 2; ++attempt) {
+  uint64_t np = 0, nh = 0;
+  const int st = CallWithGrownCapacity(2ull * K * level.mean_list() + 1024, worst, np, nh, [&](uint64_t cap, uint64_t) {
     out.table.resize(cap);
     out.maybe.resize(cap);
-    st = adl_bloom_level_multiget(lv, cache.handle(), 0, reinterpret_cast<const uint8_t *>(batch.bytes().data()),
-                                  batch.offsets().data(), K, 0, seq, out.begin.data(), out.table.data(),
-                                  out.maybe.data(), cap, &np, &out.uncached, nullptr);
-    if (st != ADL_ERR_WORKSPACE || np <= cap || np > worst) break;
-    cap = np;
-  }
+    return adl_bloom_level_multiget(lv, cache.handle(), 0, reinterpret_cast<const uint8_t *>(batch.bytes().data()),
+                                    batch.offsets().data(), K, 0, seq, out.begin.data(), out.table.data(),
+                                    out.maybe.data(), cap, &np, &out.uncached, nullptr);
+  });
   if (st != ADL_OK) {
     out = MultiGetFilterResult{};
     return FromStatus(st);
@@ -518,6 +425,9 @@ RC RevisionMultiGetFilter(FilterCache &cache, RevisionIndex &rev, const vector<s
   adl_bloom_revision *h = rev.handle();
   if (!h) return rev.device_status();
   if (!cache.handle()) return cache.status();
+  // (packed and sized here, not through PackKeys and CallWithGrownCapacity:
+  // with them this function's all-hit batches of 65 536 keys measured 3-7 %
+  // slower)
   size_t key_bytes = 0;
   for (string_view k : user_keys) key_bytes += k.size();
   KeyArena batch;
@@ -554,6 +464,37 @@ RC RevisionMultiGetFilter(FilterCache &cache, RevisionIndex &rev, const vector<s
 
 }  // namespace adl
 
+namespace {
+
+/* The test hooks' arguments: tables [t0, t1) of (pointer, length) arrays (no
+ * oids), keys [i0, i1) as views, and a result copied out to the caller's
+ * arrays (the number of pairs, or -1 when cap is too small). */
+std::vector<adl::TableRange> HookTables(const char *const *mins, const uint64_t *min_lens, const char *const *maxs,
+                                        const uint64_t *max_lens, uint32_t t0, uint32_t t1) {
+  std::vector<adl::TableRange> tabs(t1 - t0);
+  for (uint32_t t = t0; t < t1; ++t) {
+    tabs[t - t0].min_inner_key.assign(mins[t], min_lens[t]);
+    tabs[t - t0].max_inner_key.assign(maxs[t], max_lens[t]);
+  }
+  return tabs;
+}
+
+std::vector<std::string_view> HookKeys(const char *const *keys, const uint64_t *key_lens, uint32_t i0, uint32_t i1) {
+  std::vector<std::string_view> ks(i1 - i0);
+  for (uint32_t i = i0; i < i1; ++i) ks[i - i0] = std::string_view(keys[i], key_lens[i]);
+  return ks;
+}
+
+int64_t HookResult(const std::vector<uint32_t> &b, const std::vector<uint32_t> &tb, uint32_t *begin, uint32_t *table,
+                   uint64_t cap) {
+  if (tb.size() > cap) return -1;
+  std::copy(b.begin(), b.end(), begin);
+  std::copy(tb.begin(), tb.end(), table);
+  return (int64_t)tb.size();
+}
+
+}  // namespace
+
 /* Test hook (tests/test_revision_cpu.py): one LevelIndex per level over its
  * tables, a RevisionIndex over them, and its host Candidates for one batch.
  * Level l's tables are [table_begin[l], table_begin[l+1]) of mins / maxs; a
@@ -569,25 +510,15 @@ extern "C" int64_t adl_revision_index_candidates(const char *const *mins, const 
   std::vector<adl::LevelIndex *> lv(L, nullptr);
   for (uint32_t l = 0; l < L; ++l) {
     if (skip && skip[l]) continue;
-    std::vector<adl::TableRange> tabs;
-    for (uint32_t t = table_begin[l]; t < table_begin[l + 1]; ++t) {
-      tabs.emplace_back();
-      tabs.back().min_inner_key.assign(mins[t], min_lens[t]);
-      tabs.back().max_inner_key.assign(maxs[t], max_lens[t]);
-    }
-    own[l] = std::make_unique<adl::LevelIndex>(tabs);
+    own[l] = std::make_unique<adl::LevelIndex>(
+        HookTables(mins, min_lens, maxs, max_lens, table_begin[l], table_begin[l + 1]));
     lv[l] = own[l].get();
   }
   adl::RevisionIndex rev(lv);
   if (rev.status()) return -2;
-  std::vector<std::string_view> ks(K);
-  for (uint32_t i = 0; i < K; ++i) ks[i] = std::string_view(keys[i], key_lens[i]);
   std::vector<uint32_t> b, tb;
-  rev.Candidates(ks, seq, b, tb);
-  if (tb.size() > cap) return -1;
-  std::copy(b.begin(), b.end(), begin);
-  std::copy(tb.begin(), tb.end(), table);
-  return (int64_t)tb.size();
+  rev.Candidates(HookKeys(keys, key_lens, 0, K), seq, b, tb);
+  return HookResult(b, tb, begin, table, cap);
 }
 
 /* Test hook (tests/test_level_cpu.py): LevelCandidates over tables and keys
@@ -597,19 +528,9 @@ extern "C" int64_t adl_level_candidates(const char *const *mins, const uint64_t 
                                         const uint64_t *max_lens, uint32_t T, const char *const *keys,
                                         const uint64_t *key_lens, uint32_t K, int64_t seq, uint32_t *begin,
                                         uint32_t *table, uint64_t cap) {
-  std::vector<adl::TableRange> tabs(T);
-  for (uint32_t t = 0; t < T; ++t) {
-    tabs[t].min_inner_key.assign(mins[t], min_lens[t]);
-    tabs[t].max_inner_key.assign(maxs[t], max_lens[t]);
-  }
-  std::vector<std::string_view> ks(K);
-  for (uint32_t i = 0; i < K; ++i) ks[i] = std::string_view(keys[i], key_lens[i]);
   std::vector<uint32_t> b, tb;
-  adl::LevelCandidates(tabs, ks, seq, b, tb);
-  if (tb.size() > cap) return -1;
-  std::copy(b.begin(), b.end(), begin);
-  std::copy(tb.begin(), tb.end(), table);
-  return (int64_t)tb.size();
+  adl::LevelCandidates(HookTables(mins, min_lens, maxs, max_lens, 0, T), HookKeys(keys, key_lens, 0, K), seq, b, tb);
+  return HookResult(b, tb, begin, table, cap);
 }
 
 /* Test hook (tests/test_level_index_cpu.py): ONE LevelIndex over the tables,
@@ -623,23 +544,15 @@ extern "C" int64_t adl_level_index_candidates(const char *const *mins, const uin
                                               uint64_t max_index_bytes, const char *const *keys,
                                               const uint64_t *key_lens, const uint32_t *key_begin, uint32_t batches,
                                               const int64_t *seqs, uint32_t *begin, uint32_t *table, uint64_t cap) {
-  std::vector<adl::TableRange> tabs(T);
-  for (uint32_t t = 0; t < T; ++t) {
-    tabs[t].min_inner_key.assign(mins[t], min_lens[t]);
-    tabs[t].max_inner_key.assign(maxs[t], max_lens[t]);
-  }
-  adl::LevelIndex index(tabs, max_index_bytes);
+  adl::LevelIndex index(HookTables(mins, min_lens, maxs, max_lens, 0, T), max_index_bytes);
   if (index.status()) return -2;
   uint64_t total = 0;
   for (uint32_t b = 0; b < batches; ++b) {
-    std::vector<std::string_view> ks;
-    for (uint32_t i = key_begin[b]; i < key_begin[b + 1]; ++i) ks.emplace_back(keys[i], key_lens[i]);
     std::vector<uint32_t> bg, tb;
-    index.Candidates(ks, seqs[b], bg, tb);
-    if (total + tb.size() > cap) return -1;
-    std::copy(bg.begin(), bg.end(), begin + key_begin[b] + b);
-    std::copy(tb.begin(), tb.end(), table + total);
-    total += tb.size();
+    index.Candidates(HookKeys(keys, key_lens, key_begin[b], key_begin[b + 1]), seqs[b], bg, tb);
+    const int64_t n = HookResult(bg, tb, begin + key_begin[b] + b, table + total, cap - total);
+    if (n < 0) return -1;
+    total += (uint64_t)n;
   }
   return (int64_t)total;
 }

@@ -158,27 +158,26 @@ __global__ __launch_bounds__(kBlockL) void level_expand_kernel(uint64_t nkeys, L
   }
 }
 
+// selection's workspace: [region][count] per key, [block_total][block_off] per workgroup
 uint64_t ws_layout(uint64_t num_keys, uint64_t &o_count, uint64_t &o_btot, uint64_t &o_boff) {
   const uint64_t nblk = (num_keys + kBlockL - 1) / kBlockL;
-  o_count = adl_host::round_up(num_keys * 4, 256);
-  o_btot = o_count + adl_host::round_up(num_keys * 4, 256);
-  o_boff = o_btot + adl_host::round_up(nblk * 8, 256);
-  return o_boff + adl_host::round_up(nblk * 8, 256) + 256;
+  adl_host::StagePlan p;
+  p.take(num_keys * 4);
+  o_count = p.take(num_keys * 4);
+  o_btot = p.take(nblk * 8);
+  o_boff = p.take(nblk * 8);
+  return p.end + 256;
 }
 
 // the device copy, made once (under lv->mu)
 int upload_locked(adl_bloom_level *lv) {
   const adl_level::Index &ix = lv->ix;
-  uint64_t o = 0;
-  auto place = [&](uint64_t bytes) {
-    const uint64_t at = o;
-    o += adl_host::round_up(bytes + 16, 256);  // (never empty, and byte reads stay inside)
-    return at;
-  };
+  adl_host::StagePlan plan;
+  auto place = [&](uint64_t bytes) { return plan.take(bytes + 16); };  // (never empty, and byte reads stay inside)
   const uint64_t o_pref = place(16ull * ix.num_boundaries), o_bb = place(ix.bbytes.size()),
                  o_boff = place(4ull * ix.boff.size()), o_rbeg = place(4ull * ix.rbeg.size()),
                  o_rlist = place(4ull * ix.rlist.size()), o_seq = place(8ull * ix.mx_seq.size()),
-                 o_op = place(ix.mx_op.size());
+                 o_op = place(ix.mx_op.size()), o = plan.end;
   // the arrays laid out in one pinned buffer and sent as one DMA (no copy from
   // pageable memory anywhere, see Staging); the buffer is the index's size and
   // used once, so it is not a thread's staging buffer
@@ -217,18 +216,9 @@ int upload_locked(adl_bloom_level *lv) {
   return ADL_OK;
 }
 
-int ensure_uploaded(adl_bloom_level *lv) {
-  std::lock_guard<std::mutex> g(lv->mu);
-  if (!lv->uploaded) {
-    lv->upload_status = upload_locked(lv);
-    lv->uploaded = true;
-  }
-  return lv->upload_status;
-}
-
 }  // namespace
 
-int adl_host::level_ensure_uploaded(adl_bloom_level *lv) { return ensure_uploaded(lv); }
+int adl_host::level_ensure_uploaded(adl_bloom_level *lv) { return ensure_uploaded(lv, upload_locked); }
 
 int adl_host::level_scan_launch(const uint64_t *d_block_total, uint64_t nblk, uint64_t *d_block_off, uint64_t *d_total,
                                 hipStream_t st) {
@@ -249,12 +239,11 @@ int adl_host::level_select_device(adl_bloom_level *lv, const uint8_t *d_keys, co
     ADL_HIP_TRY(hipMemsetAsync(d_num_pairs, 0, 8, st));
     return ADL_OK;
   }
-  if (int rc = ensure_uploaded(lv)) return rc;
+  if (int rc = level_ensure_uploaded(lv)) return rc;
   uint8_t *ws = static_cast<uint8_t *>(d_workspace);
   uint32_t *region = reinterpret_cast<uint32_t *>(ws), *count = reinterpret_cast<uint32_t *>(ws + o_count);
   uint64_t *btot = reinterpret_cast<uint64_t *>(ws + o_btot), *boff = reinterpret_cast<uint64_t *>(ws + o_boff);
-  const LevelDev dv{lv->d_pref, lv->d_bbytes, lv->d_boff, lv->d_rbeg, lv->d_rlist,
-                    lv->d_mx_seq, lv->d_mx_op, lv->ix.num_boundaries};
+  const LevelDev dv = lv->dev();
   const KeySet ks{d_keys, d_offsets, key_stride};
   const uint64_t nblk = (num_keys + kBlockL - 1) / kBlockL;
   hipLaunchKernelGGL(level_locate_kernel, dim3((uint32_t)nblk), dim3(kBlockL), 0, st, ks, num_keys, dv, seq, region,
@@ -329,10 +318,9 @@ int adl_bloom_level_candidates_device(adl_bloom_level *level, const uint8_t *d_k
                                       uint64_t num_keys, uint32_t key_stride, int64_t seq, uint32_t *d_pair_begin,
                                       uint32_t *d_pair_table, uint64_t pair_capacity, uint64_t *d_num_pairs,
                                       void *d_workspace, uint64_t workspace_bytes, void *stream) {
-  if (!level || !d_pair_begin || !d_num_pairs || !d_workspace) return ADL_ERR_INVALID_ARG;
-  if (num_keys && (!d_keys || (!d_offsets && key_stride == 0))) return ADL_ERR_INVALID_ARG;
-  if (pair_capacity && !d_pair_table) return ADL_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(d_workspace) % 256) return ADL_ERR_INVALID_ARG;
+  if (!adl_host::candidates_args_ok(level, d_keys, d_offsets, num_keys, key_stride, d_pair_begin, d_pair_table,
+                                    pair_capacity, d_num_pairs, d_workspace))
+    return ADL_ERR_INVALID_ARG;
   return adl_host::level_select_device(level, d_keys, d_offsets, num_keys, key_stride, seq, d_pair_begin,
                                        d_pair_table, pair_capacity, d_num_pairs, d_workspace, workspace_bytes,
                                        (hipStream_t)stream);

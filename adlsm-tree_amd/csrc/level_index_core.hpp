@@ -228,23 +228,39 @@ inline void Lookup(const Index &ix, size_t K, KeyAt &&key_at, int64_t seq, uint3
   else LookupImpl<false>(ix, K, key_at, seq, begin, table);
 }
 
-/* Builds `ix` from the tables' (min, max) inner keys.  False, with nothing
- * large allocated: the index would take more than max_bytes bytes (heavily
- * overlapping tables need O(T^2) list entries), or is beyond the u32 / 2^24
- * limits of the layout. */
-inline bool Build(const std::string_view *mins, const std::string_view *maxs, size_t T, uint64_t max_bytes, Index &ix) {
+/* What Build knows before it builds any list: the tables decoded and in
+ * files_meta_ order, who enters and leaves at each boundary, and the size of
+ * the lists.  (LevelCandidates stops here when a direct scan is cheaper.) */
+struct Sweep {
+  std::vector<Decoded> mn, mx;
+  std::vector<uint32_t> asc;  // ascending min_inner_key, stable; visited in reverse
+  // the tables that enter at boundary i, in_tab[in_beg[i] .. in_beg[i+1]) in
+  // ascending min order, and those that leave at it, out_tab likewise
+  std::vector<uint32_t> in_beg, in_tab, out_beg, out_tab;
+  uint64_t total = 0, longest = 0;  // the entries of all region lists, and of the longest one
+  /* a table whose max user key sorts before its min (no real table) is never a candidate */
+  bool never(size_t t) const { return mx[t].user < mn[t].user; }
+};
+
+/* Build's first half: the boundaries of `ix`, its tables' max (seq, op), and
+ * `sw`.  A table is counted at its own max boundary whatever its max seq is (it
+ * is listed there, flagged).  False: beyond the u32 limits of the layout (sw.mn,
+ * sw.mx and sw.asc are filled even then). */
+inline bool Prepare(const std::string_view *mins, const std::string_view *maxs, size_t T, Index &ix, Sweep &sw) {
   ix = Index{};
+  sw = Sweep{};
+  sw.mn.resize(T);
+  sw.mx.resize(T);
+  for (size_t t = 0; t < T; ++t) {
+    sw.mn[t] = Decode(mins[t]);
+    sw.mx[t] = Decode(maxs[t]);
+  }
+  const std::vector<Decoded> &mn = sw.mn, &mx = sw.mx;
+  sw.asc.resize(T);
+  std::iota(sw.asc.begin(), sw.asc.end(), 0u);
+  std::stable_sort(sw.asc.begin(), sw.asc.end(), [&](uint32_t a, uint32_t b) { return Less(mn[a], mn[b]); });
   if (T >= kTableMask) return false;
   ix.num_tables = (uint32_t)T;
-  // files_meta_ order (ascending min_inner_key, stable), visited in reverse
-  std::vector<Decoded> mn(T), mx(T);
-  for (size_t t = 0; t < T; ++t) {
-    mn[t] = Decode(mins[t]);
-    mx[t] = Decode(maxs[t]);
-  }
-  std::vector<uint32_t> asc(T);
-  std::iota(asc.begin(), asc.end(), 0u);
-  std::stable_sort(asc.begin(), asc.end(), [&](uint32_t a, uint32_t b) { return Less(mn[a], mn[b]); });
   std::vector<std::string_view> B;
   B.reserve(2 * T);
   for (size_t t = 0; t < T; ++t) {
@@ -274,55 +290,78 @@ inline bool Build(const std::string_view *mins, const std::string_view *maxs, si
     ix.mx_op[t] = (uint8_t)mx[t].op;
   }
   // per boundary: the tables that enter at it (ascending min order) and leave
-  // at it.  A table whose max user key sorts before its min (no real table) is
-  // never a candidate.
-  std::vector<std::vector<uint32_t>> ins(NB), outs(NB);
-  for (uint32_t t : asc)
-    if (!(mx[t].user < mn[t].user)) ins[ix.lower_bound(mn[t].user)].push_back(t);
-  for (size_t t = 0; t < T; ++t)
-    if (!(mx[t].user < mn[t].user)) outs[ix.lower_bound(mx[t].user)].push_back((uint32_t)t);
-  // the size of the lists before any of them is built
-  uint64_t total = 0, longest = 0;
-  {
-    uint64_t active = 0;
-    for (size_t i = 0; i < NB; ++i) {
-      total += active;  // the gap before B[i]
-      active += ins[i].size();
-      total += active;  // B[i]: the tables that end here are still listed (flagged)
-      longest = std::max(longest, active);
-      active -= outs[i].size();
-    }
-    total += active;  // (0: every table has left)
+  // at it, bucketed by a counting sort
+  constexpr uint32_t kNever = ~0u;
+  std::vector<uint32_t> at_min(T, kNever), at_max(T, kNever);
+  for (size_t t = 0; t < T; ++t) {
+    if (sw.never(t)) continue;
+    at_min[t] = ix.lower_bound(mn[t].user);
+    at_max[t] = ix.lower_bound(mx[t].user);
   }
+  auto bucket = [&](const std::vector<uint32_t> &at, const uint32_t *order, std::vector<uint32_t> &beg,
+                    std::vector<uint32_t> &tab) {
+    beg.assign(NB + 2, 0);  // counted two slots up, so that the fill's cursors leave the starts behind
+    for (size_t t = 0; t < T; ++t)
+      if (at[t] != kNever) ++beg[at[t] + 2];
+    std::partial_sum(beg.begin(), beg.end(), beg.begin());
+    tab.resize(beg[NB + 1]);
+    for (size_t j = 0; j < T; ++j) {
+      const uint32_t t = order ? order[j] : (uint32_t)j;
+      if (at[t] != kNever) tab[beg[at[t] + 1]++] = t;
+    }
+  };
+  bucket(at_min, sw.asc.data(), sw.in_beg, sw.in_tab);
+  bucket(at_max, nullptr, sw.out_beg, sw.out_tab);
+  // the size of the lists before any of them is built
+  uint64_t active = 0;
+  for (size_t i = 0; i < NB; ++i) {
+    sw.total += active;  // the gap before B[i]
+    active += sw.in_beg[i + 1] - sw.in_beg[i];
+    sw.total += active;  // B[i]: the tables that end here are still listed (flagged)
+    sw.longest = std::max(sw.longest, active);
+    active -= sw.out_beg[i + 1] - sw.out_beg[i];
+  }
+  sw.total += active;  // (0: every table has left)
+  return true;
+}
+
+/* Build's second half: the region lists.  False, with nothing large
+ * allocated: see Build. */
+inline bool Finish(const Sweep &sw, uint64_t max_bytes, Index &ix) {
+  const size_t T = ix.num_tables, NB = ix.num_boundaries;
   ix.rbeg.assign(2 * NB + 2, 0);
-  if (total > 0xffffffffull) return false;
-  if (longest >= (1u << 24)) return false;  // 256 lists of a workgroup's keys add up in a u32
-  ix.longest = (uint32_t)longest;
-  if (16ull * NB + bbytes + 4ull * (NB + 1) + 4ull * (2 * NB + 2) + 4ull * total + 9ull * T > max_bytes)
+  if (sw.total > 0xffffffffull) return false;
+  if (sw.longest >= (1u << 24)) return false;  // 256 lists of a workgroup's keys add up in a u32
+  ix.longest = (uint32_t)sw.longest;
+  if (16ull * NB + ix.bbytes.size() + 4ull * (NB + 1) + 4ull * (2 * NB + 2) + 4ull * sw.total + 9ull * T > max_bytes)
     return false;
   // One sweep builds every region's list in visiting order: a table enters at
   // the front of the active list (ascending min order, so the list stays in
   // visiting order) and leaves after its max.
-  ix.rlist.reserve(total);
+  ix.rlist.resize(sw.total);
+  uint32_t *w = ix.rlist.data();
   constexpr uint32_t kNil = ~0u;
-  std::vector<uint32_t> nxt(T, kNil), prv(T, kNil);
-  std::vector<uint8_t> ends_here(T, 0);
+  std::vector<uint32_t> nxt(T, kNil), prv(T, kNil), flag(T, 0);  // flag: kGoneAtMaxFlag where the table ends
   uint32_t head = kNil;
   auto record = [&](size_t r) {
-    for (uint32_t t = head; t != kNil; t = nxt[t]) ix.rlist.push_back(ends_here[t] ? t | kGoneAtMaxFlag : t);
-    ix.rbeg[r + 1] = (uint32_t)ix.rlist.size();
+    for (uint32_t t = head; t != kNil; t = nxt[t]) *w++ = t | flag[t];
+    ix.rbeg[r + 1] = (uint32_t)(w - ix.rlist.data());
   };
   for (size_t i = 0; i < NB; ++i) {
+    const uint32_t *const in0 = sw.in_tab.data() + sw.in_beg[i], *const in1 = sw.in_tab.data() + sw.in_beg[i + 1];
+    const uint32_t *const out0 = sw.out_tab.data() + sw.out_beg[i], *const out1 = sw.out_tab.data() + sw.out_beg[i + 1];
     record(2 * i);
-    for (uint32_t t : ins[i]) {
+    for (const uint32_t *p = in0; p != in1; ++p) {
+      const uint32_t t = *p;
       nxt[t] = head;
       prv[t] = kNil;
       if (head != kNil) prv[head] = t;
       head = t;
     }
-    for (uint32_t t : outs[i]) ends_here[t] = 1;
+    for (const uint32_t *p = out0; p != out1; ++p) flag[*p] = kGoneAtMaxFlag;
     record(2 * i + 1);
-    for (uint32_t t : outs[i]) {
+    for (const uint32_t *p = out0; p != out1; ++p) {
+      const uint32_t t = *p;
       if (prv[t] != kNil) nxt[prv[t]] = nxt[t];
       else head = nxt[t];
       if (nxt[t] != kNil) prv[nxt[t]] = prv[t];
@@ -330,6 +369,16 @@ inline bool Build(const std::string_view *mins, const std::string_view *maxs, si
   }
   record(2 * NB);
   return true;
+}
+
+/* Builds `ix` from the tables' (min, max) inner keys.  False, with nothing
+ * large allocated: the index would take more than max_bytes bytes (heavily
+ * overlapping tables need O(T^2) list entries), or is beyond the u32 / 2^24
+ * limits of the layout. */
+inline bool Build(const std::string_view *mins, const std::string_view *maxs, size_t T, uint64_t max_bytes, Index &ix) {
+  Sweep sw;
+  if (T >= kTableMask) return ix = Index{}, false;
+  return Prepare(mins, maxs, T, ix, sw) && Finish(sw, max_bytes, ix);
 }
 
 }  // namespace adl_level

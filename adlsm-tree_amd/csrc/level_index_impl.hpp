@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "level_index_core.hpp"
+#include "level_index_device.hpp"
 
 // The host copy is immutable after creation; the device copy (one allocation,
 // `d_blob`) is made by the first device call, under `mu`, and immutable from
@@ -30,9 +31,36 @@ struct adl_bloom_level {
   const uint32_t *d_rlist = nullptr;
   const int64_t *d_mx_seq = nullptr;  // per table
   const uint8_t *d_mx_op = nullptr;
+  // what the kernels take (valid once uploaded)
+  adl_level_dev::LevelDev dev() const {
+    return {d_pref, d_bbytes, d_boff, d_rbeg, d_rlist, d_mx_seq, d_mx_op, ix.num_boundaries};
+  }
 };
 
 namespace adl_host {
+
+// The argument checks of adl_bloom_level_candidates_device and
+// adl_bloom_revision_candidates_device, `handle` the level or the revision.
+inline bool candidates_args_ok(const void *handle, const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t num_keys,
+                               uint32_t key_stride, const uint32_t *d_pair_begin, const uint32_t *d_pair_table,
+                               uint64_t pair_capacity, const uint64_t *d_num_pairs, const void *d_workspace) {
+  if (!handle || !d_pair_begin || !d_num_pairs || !d_workspace) return false;
+  if (num_keys && (!d_keys || (!d_offsets && key_stride == 0))) return false;
+  if (pair_capacity && !d_pair_table) return false;
+  return reinterpret_cast<uintptr_t>(d_workspace) % 256 == 0;
+}
+
+// The device copy of a level or a revision: made by upload(h), under h->mu, on
+// the handle's first device call; every call gets that upload's status.
+template <class Handle, class Upload>
+int ensure_uploaded(Handle *h, Upload &&upload) {
+  std::lock_guard<std::mutex> g(h->mu);
+  if (!h->uploaded) {
+    h->upload_status = upload(h);
+    h->uploaded = true;
+  }
+  return h->upload_status;
+}
 
 // Uploads the index if this is the level's first device call (synchronous,
 // on a stream of the calling thread's), then enqueues selection on `st`:

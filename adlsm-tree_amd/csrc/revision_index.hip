@@ -170,12 +170,13 @@ __global__ __launch_bounds__(kBlockL) void revision_expand_kernel(uint64_t nkeys
 uint64_t ws_layout(uint32_t live, uint64_t num_keys, uint64_t &o_cntl, uint64_t &o_count, uint64_t &o_btot,
                    uint64_t &o_boff) {
   const uint64_t nblk = (num_keys + kBlockL - 1) / kBlockL;
-  const uint64_t per_level = adl_host::round_up((uint64_t)live * num_keys * 4, 256);
-  o_cntl = per_level;
-  o_count = o_cntl + per_level;
-  o_btot = o_count + adl_host::round_up(num_keys * 4, 256);
-  o_boff = o_btot + adl_host::round_up(nblk * 8, 256);
-  return o_boff + adl_host::round_up(nblk * 8, 256) + 256;
+  adl_host::StagePlan p;
+  p.take((uint64_t)live * num_keys * 4);
+  o_cntl = p.take((uint64_t)live * num_keys * 4);
+  o_count = p.take(num_keys * 4);
+  o_btot = p.take(nblk * 8);
+  o_boff = p.take(nblk * 8);
+  return p.end + 256;
 }
 
 // the device copy, made once (under rev->mu); every level's own copy first
@@ -190,8 +191,7 @@ int upload_locked(adl_bloom_revision *rev) {
     if (!lv || lv->ix.num_tables == 0) continue;
     rc = adl_host::level_ensure_uploaded(lv);
     h->base[nl] = rev->table_base[l];
-    h->lv[nl] = LevelDev{lv->d_pref, lv->d_bbytes, lv->d_boff, lv->d_rbeg, lv->d_rlist,
-                         lv->d_mx_seq, lv->d_mx_op, lv->ix.num_boundaries};
+    h->lv[nl] = lv->dev();
     ++nl;
   }
   h->nl = nl;
@@ -208,15 +208,6 @@ int upload_locked(adl_bloom_revision *rev) {
   return rc;
 }
 
-int ensure_uploaded(adl_bloom_revision *rev) {
-  std::lock_guard<std::mutex> g(rev->mu);
-  if (!rev->uploaded) {
-    rev->upload_status = upload_locked(rev);
-    rev->uploaded = true;
-  }
-  return rev->upload_status;
-}
-
 }  // namespace
 
 int adl_host::revision_select_device(adl_bloom_revision *rev, const uint8_t *d_keys, const uint64_t *d_offsets,
@@ -231,7 +222,7 @@ int adl_host::revision_select_device(adl_bloom_revision *rev, const uint8_t *d_k
     ADL_HIP_TRY(hipMemsetAsync(d_num_pairs, 0, 8, st));
     return ADL_OK;
   }
-  if (int rc = ensure_uploaded(rev)) return rc;
+  if (int rc = ensure_uploaded(rev, upload_locked)) return rc;
   uint8_t *ws = static_cast<uint8_t *>(d_workspace);
   uint32_t *region = reinterpret_cast<uint32_t *>(ws), *cntl = reinterpret_cast<uint32_t *>(ws + o_cntl),
            *count = reinterpret_cast<uint32_t *>(ws + o_count);
@@ -311,10 +302,9 @@ int adl_bloom_revision_candidates_device(adl_bloom_revision *rev, const uint8_t 
                                          uint64_t num_keys, uint32_t key_stride, int64_t seq, uint32_t *d_pair_begin,
                                          uint32_t *d_pair_table, uint64_t pair_capacity, uint64_t *d_num_pairs,
                                          void *d_workspace, uint64_t workspace_bytes, void *stream) {
-  if (!rev || !d_pair_begin || !d_num_pairs || !d_workspace) return ADL_ERR_INVALID_ARG;
-  if (num_keys && (!d_keys || (!d_offsets && key_stride == 0))) return ADL_ERR_INVALID_ARG;
-  if (pair_capacity && !d_pair_table) return ADL_ERR_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(d_workspace) % 256) return ADL_ERR_INVALID_ARG;
+  if (!adl_host::candidates_args_ok(rev, d_keys, d_offsets, num_keys, key_stride, d_pair_begin, d_pair_table,
+                                    pair_capacity, d_num_pairs, d_workspace))
+    return ADL_ERR_INVALID_ARG;
   return adl_host::revision_select_device(rev, d_keys, d_offsets, num_keys, key_stride, seq, d_pair_begin,
                                           d_pair_table, pair_capacity, d_num_pairs, d_workspace, workspace_bytes,
                                           (hipStream_t)stream);

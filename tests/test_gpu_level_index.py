@@ -443,6 +443,36 @@ def test_level_multiget_through_cache(dev, ab, oracle, K):
         cache.close()
 
 
+def test_level_multiget_short_capacity_releases_its_pins(dev, ab, oracle):
+    """adl_bloom_level_multiget returning ADL_ERR_WORKSPACE has unpinned the
+    level's tables: removed right after, their arena ranges are free at once
+    (a range still pinned would stay in use).  The next full-capacity call on
+    the re-populated cache answers as probe_fanout does on the same lists."""
+    _, tabs = _multiget_level(oracle)
+    tabs = tabs[:4]
+    oids = [t["oid"] for t in tabs]
+    keys = [t["members"][i] for t in tabs for i in (100, 500)]  # 8 keys, each inside its table's range
+    data, offs = oracle.pack(keys)
+    cache = ab.FilterCache(16 << 20, max_tables=16)
+    lv = ab.LevelIndex([t["range"] for t in tabs], oids=oids)
+    try:
+        for t in tabs:
+            cache.put(t["oid"], t["block"])
+        rc, _, _, _, n, _ = lv.multiget_status(cache, data, offs, pair_capacity=1)
+        assert rc == ab.ADL_ERR_WORKSPACE and n >= len(keys)
+        assert all(cache.remove(o) for o in oids)
+        assert cache.stats() == (0, 0)
+        for t in tabs:
+            cache.put(t["oid"], t["block"])
+        pb, pt, out, unc = lv.multiget(cache, data, offs)
+        assert (np.diff(pb.astype(np.int64)) > 0).all() and len(pt) == n and unc == 0
+        ref, ref_unc = cache.probe_fanout(oids, pb, pt, data, offs)
+        assert out.tobytes() == ref.tobytes() and ref_unc == 0
+    finally:
+        lv.close()
+        cache.close()
+
+
 def test_level_index_binary(dev):
     """bin/level_index_test: LevelMultiGetFilter(cache, index, ...) on the host
     copy (300 keys) and on the device path (3 000 keys) equals

@@ -222,6 +222,52 @@ def test_filter_cache_completion_fault(dev, ab, oracle):
     cache.close()
 
 
+@pytest.mark.parametrize("call", ["probe_server", "probe_mapped", "fanout_mapped"])
+def test_filter_cache_completion_fault_releases_its_pins(dev, ab, oracle, knobs, call):
+    """The error return after a simulated completion failure has unpinned the
+    probed tables: removed right after, their arena ranges are free at once (a
+    range still pinned would stay in use).  probe with 2 keys, through the
+    resident server and, with the server off, through the mapped buffer;
+    probe_fanout with 70 pairs: above the server's limit and still mapped."""
+    if call == "probe_mapped":
+        knobs.set("ADL_BLOOM_PROBE_SERVER", "0")
+    (k0, b0), (k1, b1) = _block(oracle, 3200, 2000), _block(oracle, 3201, 2000)
+    oids = [b"t0", b"t1"]
+    cache = ab.FilterCache(8 << 20, max_tables=8)
+    try:
+        if call == "fanout_mapped":
+            q = np.concatenate([k0[:18], k1[:17]])  # 35 keys, both tables each
+            begin, table = np.arange(0, 71, 2, dtype=np.uint32), np.tile(np.array([0, 1], np.uint32), 35)
+            want = np.stack([oracle.probe(q, oracle.keys2block(k0)), oracle.probe(q, oracle.keys2block(k1))], 1).ravel()
+
+            def ask():
+                return cache.probe_fanout(oids, begin, table, q)
+        else:
+            q, table = np.stack([k0[5], k1[7]]), np.array([0, 1], np.uint32)
+            want = np.ones(2, np.uint8)
+
+            def ask():
+                return cache.probe(oids, table, q)
+        for o, b in zip(oids, (b0, b1)):
+            cache.put(o, b)
+        got, unc = ask()
+        assert unc == 0 and np.array_equal(got, want)
+        ab.test_fault(ab.TEST_FAULT_CACHE_COMPLETION, 0)
+        try:
+            with pytest.raises(ab.AdlBloomError):
+                ask()
+        finally:
+            ab.test_fault(ab.TEST_FAULT_CACHE_COMPLETION, -1)
+        assert all(cache.remove(o) for o in oids)
+        assert cache.stats() == (0, 0)
+        for o, b in zip(oids, (b0, b1)):
+            cache.put(o, b)
+        got, unc = ask()
+        assert unc == 0 and np.array_equal(got, want)
+    finally:
+        cache.close()
+
+
 @pytest.mark.parametrize("stride", [8, 24])
 def test_pipeline_fixed_stride_unaligned_groups(dev, ab, oracle, stride):
     """adl_bloom_build_segmented with fixed-stride keys: more than 8 filters (so

@@ -567,6 +567,47 @@ def test_revision_multiget_through_cache(dev, ab, oracle, K):
         cache.close()
 
 
+def test_revision_multiget_short_capacities_release_their_pins(dev, ab, oracle):
+    """adl_bloom_revision_multiget returning ADL_ERR_WORKSPACE, for too few hits
+    and for too few pairs, has unpinned every level's tables: removed right
+    after, their arena ranges are free at once.  The next full-capacity call on
+    the re-populated cache keeps the pairs probe_fanout answers 1 on the same
+    lists."""
+    _, tabs, split = _multiget_revision(oracle)
+    tabs, split = tabs[:4], split[:2]
+    oids = [t["oid"] for t in tabs]
+    keys = [t["members"][i] for t in tabs for i in (100, 500)]  # 8 keys, each inside its table's range
+    data, offs = oracle.pack(keys)
+    cache = ab.FilterCache(16 << 20, max_tables=16)
+    levels = [ab.LevelIndex([tabs[t]["range"] for t in ids], oids=[oids[t] for t in ids]) for ids in split]
+    rev = ab.Revision(levels)
+    try:
+        for t in tabs:
+            cache.put(t["oid"], t["block"])
+        rc, _, _, nh, npairs, _ = rev.multiget_status(cache, data, offs, hit_capacity=1)
+        assert rc == ab.ADL_ERR_WORKSPACE and npairs >= nh >= len(keys)
+        rc, _, _, _, np2, _ = rev.multiget_status(cache, data, offs, pair_capacity=1)
+        assert rc == ab.ADL_ERR_WORKSPACE and np2 == npairs
+        assert all(cache.remove(o) for o in oids)
+        assert cache.stats() == (0, 0)
+        for t in tabs:
+            cache.put(t["oid"], t["block"])
+        hb, ht, unc = rev.multiget(cache, data, offs)
+        per = [lv.multiget(cache, data, offs) for lv in levels]
+        begin, flat = rk.csr([[ids[0] + int(t) for ids, (pb, pt, _, _) in zip(split, per)
+                               for t in pt[int(pb[i]):int(pb[i + 1])]] for i in range(len(keys))])
+        assert (np.diff(begin.astype(np.int64)) > 0).all() and len(flat) == npairs
+        ref, ref_unc = cache.probe_fanout(oids, begin, flat, data, offs)
+        want_b, want_t = _hits_of(begin, flat, ref)
+        assert np.array_equal(hb, want_b) and np.array_equal(ht, want_t) and len(ht) == nh
+        assert unc == ref_unc == 0
+    finally:
+        rev.close()
+        for lv in levels:
+            lv.close()
+        cache.close()
+
+
 def test_revision_binary(dev):
     """bin/revision_test: RevisionMultiGetFilter on the per-level loop (300
     keys) and on the single device call (3 000 keys) equals one

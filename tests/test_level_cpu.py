@@ -47,8 +47,8 @@ def candidates(f, tables, keys, seq):
     return [list(table[begin[i]:begin[i + 1]]) for i in range(len(keys))]
 
 
-@pytest.mark.parametrize("seed", range(32))
-def test_level_candidates_vs_oracle(lvl, oracle, seed):
+def seeded_level(oracle, seed):
+    """-> (tables, keys, seq): 0 to 39 tables over few user keys, with ties; 65 keys, absent ones among them."""
     rng = np.random.default_rng(seed)
     users = sorted({bytes(rng.integers(97, 101, int(rng.integers(1, 4))).astype(np.uint8)) for _ in range(30)})
     T = int(rng.integers(0, 40))
@@ -66,6 +66,12 @@ def test_level_candidates_vs_oracle(lvl, oracle, seed):
     keys = [users[int(i)] for i in rng.integers(0, len(users), 60)]
     keys += [b"", b"a", b"zzz", users[0] + b"\x00", users[-1] + b"\xff"]
     seq = int(rng.choice([2**63 - 1, 25, 0]))
+    return tables, keys, seq
+
+
+@pytest.mark.parametrize("seed", range(32))
+def test_level_candidates_vs_oracle(lvl, oracle, seed):
+    tables, keys, seq = seeded_level(oracle, seed)
     got = candidates(lvl, tables, keys, seq)
     for i, k in enumerate(keys):
         assert got[i] == oracle.level_candidates(tables, k, seq), (i, k)

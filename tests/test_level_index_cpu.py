@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from levelkeys import P40, inner, max_tail, special_users
+from test_level_cpu import seeded_level
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "adlsm-tree_amd", "lib", "libadlfilterblock.so")
@@ -122,6 +123,19 @@ def test_one_index_answers_batches_at_several_seqs(mirror, oracle, seed):
             assert fresh[i] == want, (seq, i, k)
             dropped_somewhere |= want != oracle.level_candidates(tables, k, 2**63 - 1)
     assert dropped_somewhere  # the batches do differ by seq
+
+
+@pytest.mark.parametrize("seed", range(32))
+def test_fresh_and_index_agree_on_the_seeded_levels(mirror, oracle, seed):
+    """LevelCandidates builds the index it looks up (or scans the tables
+    directly): on test_level_cpu.py's 32 levels, 0 to 39 tables, it returns the
+    begin / table arrays of one kept LevelIndex at seq 0, 25 and 2^63 - 1."""
+    f, g = mirror
+    tables, keys, _ = seeded_level(oracle, seed)
+    seqs = (0, 25, 2**63 - 1)
+    kept = index_candidates(g, tables, [(keys, seq) for seq in seqs])
+    for seq, per_key in zip(seqs, kept):
+        assert fresh_candidates(f, tables, keys, seq) == per_key, seq
 
 
 def test_equality_op_cases_explicit(mirror, oracle):
