@@ -58,7 +58,11 @@ EXPORTS = (
     "adl_bloom_revision_candidates_workspace_bytes", "adl_bloom_revision_candidates_device",
     "adl_bloom_probe_fanout_hits_workspace_bytes", "adl_bloom_probe_fanout_hits_device",
     "adl_bloom_revision_multiget",
+    "adl_bloom_hits_by_table_workspace_bytes", "adl_bloom_hits_by_table_device", "adl_bloom_revision_read_plan",
 )
+
+# entries per workgroup of the grouping kernels (csrc/read_plan.hip, kTile): a tile of the radix sort
+HITS_TILE = 2048
 
 _LIB = None
 
@@ -138,6 +142,11 @@ def lib() -> ctypes.CDLL:
         "adl_bloom_revision_multiget": (ctypes.c_int, [vp, vp, u32, vp, vp, u64, u32, ctypes.c_int64, vp, vp, u64,
                                                         ctypes.POINTER(u64), u64, ctypes.POINTER(u64),
                                                         ctypes.POINTER(u64), vp]),
+        "adl_bloom_hits_by_table_workspace_bytes": (u64, [u64, u64, u32]),
+        "adl_bloom_hits_by_table_device": (ctypes.c_int, [vp, vp, u64, u32, vp, vp, u64, vp, u64, vp, vp, u64, vp]),
+        "adl_bloom_revision_read_plan": (ctypes.c_int, [vp, vp, u32, vp, vp, u64, u32, ctypes.c_int64, vp, vp, u64,
+                                                         ctypes.POINTER(u64), vp, u64, ctypes.POINTER(u64), u64,
+                                                         ctypes.POINTER(u64), ctypes.POINTER(u64), vp]),
         "adl_bloom_probe_device": (ctypes.c_int, [vp, vp, u64, u32, i32, vp, u64, vp, vp]),
         "adl_bloom_probe_batch_workspace_bytes": (u64, [u64, u32, i32, u32]),
         "adl_bloom_probe_batch_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, i32, vp, vp, u64, vp]),
@@ -483,6 +492,31 @@ def probe_fanout_hits(keys, pair_begin, pair_filter, bitmaps, bitmap_off, offset
                                                     bits_per_key, _dptr(hb), _dptr(hf), cap, _dptr(nh), _dptr(ws),
                                                     wsb, _stream(stream)), "adl_bloom_probe_fanout_hits_device")
     return hb, hf[:cap], nh
+
+
+def hits_by_table(hit_begin, hit_table, num_tables: int, entry_capacity: int | None = None,
+                  group_capacity: int | None = None, stream=None):
+    """probe_fanout_hits' output (device int32 tensors read as uint32: hit_begin has n+1 entries) grouped by
+    table: (group_table int32[group_capacity], group_begin int32[group_capacity+1], entry_key
+    int32[entry_capacity], counts int64[2] = hits H, groups G) device tensors read as unsigned -- the G tables
+    with a hit ascending, and entry_key[group_begin[g]:group_begin[g+1]] the keys that hit group_table[g],
+    ascending.  Enqueued on `stream` without a synchronise.  entry_capacity: default hit_table's length;
+    group_capacity: default min(num_tables, entry_capacity)."""
+    torch = _torch()
+    n = hit_begin.numel() - 1
+    ecap = hit_table.numel() if entry_capacity is None else int(entry_capacity)
+    gcap = min(int(num_tables), ecap) if group_capacity is None else int(group_capacity)
+    wsb = lib().adl_bloom_hits_by_table_workspace_bytes(n, ecap, num_tables)
+    with _on(stream):
+        gt = torch.empty(max(gcap, 1), dtype=torch.int32, device=hit_begin.device)
+        gbeg = torch.empty(gcap + 1, dtype=torch.int32, device=hit_begin.device)
+        ek = torch.empty(max(ecap, 1), dtype=torch.int32, device=hit_begin.device)
+        counts = torch.empty(2, dtype=torch.int64, device=hit_begin.device)
+        ws = empty_device(wsb, hit_begin.device)
+    _check(lib().adl_bloom_hits_by_table_device(_dptr(hit_begin), _dptr(hit_table), n, num_tables, _dptr(gt),
+                                                _dptr(gbeg), gcap, _dptr(ek), ecap, _dptr(counts), _dptr(ws), wsb,
+                                                _stream(stream)), "adl_bloom_hits_by_table_device")
+    return gt[:gcap], gbeg, ek[:ecap], counts
 
 
 def probe_batch(keys, filter_id, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10, stream=None,
@@ -973,6 +1007,38 @@ class Revision:
         rc, hb, ht, _, _, unc = self.multiget_status(cache, keys, offsets, seq, filter, None, 0, stream)
         _check(rc, "adl_bloom_revision_multiget")
         return hb, ht, unc
+
+    def read_plan_status(self, cache: "FilterCache", keys: np.ndarray, offsets=None, seq: int = 2**63 - 1,
+                         filter: int = 0, entry_capacity: int | None = None, group_capacity: int | None = None,
+                         pair_capacity: int = 0, stream=None):
+        """adl_bloom_revision_read_plan: (status, group_table, group_begin, entry_key, num_groups, num_hits,
+        num_pairs, uncached).  entry_capacity: default n * the longest list; group_capacity: default the
+        revision's tables.  The arrays start as 0xA5 bytes; without status 0 nothing is written to them."""
+        keep, kp, po, n, stride = _host_keys(keys, offsets)
+        _, base, longest = self.stats()
+        ecap = n * longest if entry_capacity is None else int(entry_capacity)
+        gcap = int(base[-1]) if group_capacity is None else int(group_capacity)
+        gt = np.full(max(gcap, 1), 0xA5A5A5A5, dtype=np.uint32)
+        gbeg = np.full(gcap + 1, 0xA5A5A5A5, dtype=np.uint32)
+        ek = np.full(max(ecap, 1), 0xA5A5A5A5, dtype=np.uint32)
+        ng, nh, npairs, unc = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        rc = lib().adl_bloom_revision_read_plan(self._h, cache._h, filter, kp, po, n, stride, seq, gt.ctypes.data,
+                                                gbeg.ctypes.data, gcap, ctypes.byref(ng), ek.ctypes.data, ecap,
+                                                ctypes.byref(nh), int(pair_capacity), ctypes.byref(npairs),
+                                                ctypes.byref(unc), _host_stream(stream))
+        if rc == ADL_OK:
+            gt, gbeg, ek = gt[:ng.value], gbeg[:ng.value + 1], ek[:nh.value]
+        return rc, gt, gbeg, ek, ng.value, nh.value, npairs.value, unc.value
+
+    def read_plan(self, cache: "FilterCache", keys: np.ndarray, offsets=None, seq: int = 2**63 - 1, filter: int = 0,
+                  stream=None):
+        """Revision multi-get as a read plan: (group_table, group_begin, entry_key, uncached) -- the tables to
+        open, global ids ascending (the levels ascending), and for table group_table[g] the indices of the
+        batch's keys to look up in it, entry_key[group_begin[g]:group_begin[g+1]], ascending."""
+        rc, gt, gbeg, ek, _, _, _, unc = self.read_plan_status(cache, keys, offsets, seq, filter, None, None, 0,
+                                                               stream)
+        _check(rc, "adl_bloom_revision_read_plan")
+        return gt, gbeg, ek, unc
 
     def close(self):
         if self._h:

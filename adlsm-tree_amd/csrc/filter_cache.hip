@@ -763,4 +763,123 @@ int adl_bloom_revision_multiget(adl_bloom_revision *rev, adl_bloom_filter_cache 
   }
 }
 
+// The revision multi-get that returns a read plan (read_plan.hip): the pieces
+// of adl_bloom_revision_multiget in the same order, then the hits grouped by
+// table on the device.  The key-major hit arrays stay in device scratch beside
+// the candidate pairs, sized for as many hits as pairs, so the grouping is
+// never short of room there and both totals are exact whatever the caller's
+// capacities are; what comes back is the counts, then the groups and entries
+// they call for.
+int adl_bloom_revision_read_plan(adl_bloom_revision *rev, adl_bloom_filter_cache *c, uint32_t filter,
+                                 const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t num_keys,
+                                 uint32_t key_stride, int64_t seq, uint32_t *h_group_table, uint32_t *h_group_begin,
+                                 uint64_t group_capacity, uint64_t *num_groups, uint32_t *h_entry_key,
+                                 uint64_t entry_capacity, uint64_t *num_hits, uint64_t pair_capacity,
+                                 uint64_t *num_pairs, uint64_t *h_uncached, void *stream) {
+  if (!rev || !c || !num_groups || !num_hits || !num_pairs || !h_group_begin) return ADL_ERR_INVALID_ARG;
+  *num_groups = *num_hits = *num_pairs = 0;
+  if (h_uncached) *h_uncached = 0;
+  if (num_keys == 0) {
+    h_group_begin[0] = 0;
+    return ADL_OK;
+  }
+  if (!h_keys || (!h_offsets && key_stride == 0) || (group_capacity && !h_group_table) ||
+      (entry_capacity && !h_entry_key))
+    return ADL_ERR_INVALID_ARG;
+  const uint32_t num_tables = rev->table_base.back();
+  for (adl_bloom_level *lv : rev->levels)
+    if (lv && lv->ix.num_tables && lv->oids.size() != lv->ix.num_tables) return ADL_ERR_INVALID_ARG;  // no oids
+  if (num_keys >= 0xffffffffull) return ADL_ERR_TOO_LARGE;
+  try {
+    hipStream_t st = adl_host::sync_stream(stream);
+    const uint64_t worst = std::min<uint64_t>(num_keys * (uint64_t)rev->longest, 0xffffffffull);
+    const uint64_t cap = pair_capacity ? std::min<uint64_t>(pair_capacity, 0xffffffffull) : worst;
+    const uint64_t gcap = std::min<uint64_t>(num_tables, cap);  // (no more groups than tables, or than hits)
+    const uint64_t ecap = std::min(entry_capacity, cap);        // what the host buffer may have to hold
+    // 1. under the lock: every level's tables' ranges and k, pinned and marked used
+    Resolved &res = t_res;
+    PinScope pins(c, res);
+    resolve_levels(c, rev->levels.data(), rev->levels.size(), num_tables, filter, res);
+    // 2. without the lock: keys, offsets and the range and k tables in one H2D;
+    //    selection, probe + hit count, scan, compaction, grouping; then the
+    //    results: num_pairs, num_hits, H and G | the group arrays | the entries
+    //    | the hit lists, the candidate pairs and scratch, on the device only
+    const uint64_t wsc = adl_bloom_revision_candidates_workspace_bytes(rev, num_keys);
+    const uint64_t wsh = adl_bloom_probe_fanout_hits_workspace_bytes(num_keys, cap);
+    const uint64_t wsg = adl_bloom_hits_by_table_workspace_bytes(num_keys, cap, num_tables);
+    adl_host::StagePlan plan;
+    const adl_host::KeyBlock kb(plan, h_offsets, num_keys, key_stride);
+    const TableBlock tb(plan, res);
+    const uint64_t o_np = plan.take(32);  // the end of the upload
+    const uint64_t o_gb = plan.take((gcap + 1) * 4);
+    const uint64_t o_gt = plan.take(gcap * 4);
+    const uint64_t o_ek = plan.take(cap * 4);
+    const uint64_t o_back = o_ek + adl_host::round_up(ecap * 4, 256);  // the end of what comes back
+    const uint64_t o_hb = plan.take((num_keys + 1) * 4);
+    const uint64_t o_ht = plan.take(cap * 4);
+    const uint64_t o_pb = plan.take((num_keys + 1) * 4);
+    const uint64_t o_pt = plan.take(cap * 4);
+    const uint64_t o_wsc = plan.take(wsc);
+    const uint64_t o_wsh = plan.take(wsh);
+    const uint64_t o_wsg = plan.take(wsg);
+    // the group arrays of a revision of a few thousand tables ride with the counts
+    const bool groups_fixed = gcap * 8 <= (64u << 10);
+    adl_host::Staging &sg = adl_host::t_stage;
+    int rc = sg.reserve(o_back, plan.end);
+    uint8_t *hbuf = sg.host, *dbuf = sg.dev;
+    if (rc == ADL_OK) {
+      kb.fill(hbuf, h_keys, h_offsets);
+      tb.fill(hbuf, res);
+      if (hipMemcpyAsync(dbuf, hbuf, o_np, hipMemcpyHostToDevice, st) != hipSuccess) rc = ADL_ERR_DEVICE;
+    }
+    auto d32 = [&](uint64_t at) { return reinterpret_cast<uint32_t *>(dbuf + at); };
+    if (rc == ADL_OK)
+      rc = adl_host::revision_select_device(rev, dbuf, kb.offsets(dbuf), num_keys, key_stride, seq, d32(o_pb),
+                                            d32(o_pt), cap, reinterpret_cast<uint64_t *>(dbuf + o_np), dbuf + o_wsc,
+                                            wsc, st);
+    if (rc == ADL_OK)  // (the kernels stop at cap pairs whatever pair_begin says)
+      rc = adl_host::probe_fanout_hits_device(dbuf, kb.offsets(dbuf), num_keys, key_stride, d32(o_pb), d32(o_pt), cap,
+                                              num_tables, c->arena, tb.begin(dbuf), tb.begin(dbuf) + num_tables, 10,
+                                              tb.k(dbuf), d32(o_hb), d32(o_ht), cap,
+                                              reinterpret_cast<uint64_t *>(dbuf + o_np + 8), dbuf + o_wsh, wsh, st);
+    if (rc == ADL_OK)
+      rc = adl_host::hits_by_table_device(d32(o_hb), d32(o_ht), num_keys, num_tables, d32(o_gt), d32(o_gb), gcap,
+                                          d32(o_ek), cap, reinterpret_cast<uint64_t *>(dbuf + o_np + 16),
+                                          dbuf + o_wsg, wsg, st);
+    uint64_t np = 0, nh = 0, ng = 0;
+    auto fits = [&] { return np <= cap && nh <= entry_capacity && ng <= group_capacity; };
+    rc = fetch_count_first(sg, o_np, groups_fixed ? o_ek : o_gb, o_back, st, rc, [&](auto piece) {
+      memcpy(&np, hbuf + o_np, 8);
+      memcpy(&nh, hbuf + o_np + 16, 8);
+      memcpy(&ng, hbuf + o_np + 24, 8);
+      if (!fits()) return;
+      if (!groups_fixed) {
+        piece(o_gb, (ng + 1) * 4);
+        piece(o_gt, ng * 4);
+      }
+      piece(o_ek, nh * 4);
+    });
+    // 3. the kernels and the copies are done: report
+    if (rc) return rc;
+    *num_pairs = np;
+    if (np > 0xffffffffull) return ADL_ERR_TOO_LARGE;
+    if (np > cap) return ADL_ERR_WORKSPACE;  // (the hits of the first cap pairs only: nothing else is reported)
+    *num_hits = nh;
+    *num_groups = ng;
+    if (!fits()) return ADL_ERR_WORKSPACE;
+    const uint32_t *gb = reinterpret_cast<const uint32_t *>(hbuf + o_gb);
+    const uint32_t *gt = reinterpret_cast<const uint32_t *>(hbuf + o_gt);
+    uint64_t uncached = 0;
+    for (uint64_t g = 0; g < ng; ++g)
+      if (!res.cached[gt[g]]) uncached += gb[g + 1] - gb[g];
+    memcpy(h_group_begin, gb, (ng + 1) * 4);
+    if (ng) memcpy(h_group_table, gt, ng * 4);
+    if (nh) memcpy(h_entry_key, hbuf + o_ek, nh * 4);
+    if (h_uncached) *h_uncached = uncached;
+    return ADL_OK;
+  } catch (...) {
+    return ADL_ERR_OUT_OF_MEMORY;
+  }
+}
+
 }  // extern "C"

@@ -145,6 +145,34 @@ uint64_t RevisionDeviceMinKeys(size_t live_levels) {
   return live_levels <= 1 ? 16000 : live_levels == 2 ? 2000 : live_levels <= 4 ? 1000 : 500;
 }
 
+/* The batch size from which RevisionReadPlanFilter makes the one device call
+ * (adl_bloom_revision_read_plan); 0 = never.  The environment's threshold, as
+ * RevisionDeviceMinKeys reads it, holds here too.  Otherwise never below that
+ * function's crossover, and never below the measured floor for the revision's
+ * number of tables ("Read plan"; profiles/read_plan/summary.txt):
+ * the smallest measured batch from which the call did not lose to
+ * RevisionMultiGetFilter + GroupHitsByTable by more than the run-to-run spread
+ * on absent-key batches (next to no hits: the grouping's launches buy nothing)
+ * and won on batches whose every pair is a hit.  Up to 256 tables the sort is
+ * one pass and the grouping four launches: it loses 10 us on absent batches at
+ * 1 000 keys, ties at 3 000 (6 us, inside the spread) and wins from there (11
+ * and 31 us on absent, 82 to 2 400 us on all-hit batches).  Beyond 256 tables
+ * it is ten launches or more: absent batches lose 17-23 us up to 16 000 keys
+ * and tie at 65 536, where all-hit batches win 2.1 ms (47 and 480 us at 3 000
+ * and 16 000, which this floor forgoes rather than tax hit-free batches). */
+uint64_t ReadPlanDeviceMinKeys(size_t live_levels, uint32_t num_tables) {
+  const uint64_t rev = RevisionDeviceMinKeys(live_levels);
+  static const bool forced = [] {
+    for (const char *name : {"ADL_BLOOM_REVISION_DEVICE_MIN_KEYS", "ADL_BLOOM_LEVEL_DEVICE_MIN_KEYS"}) {
+      const char *e = getenv(name);
+      if (e && *e) return true;
+    }
+    return false;
+  }();
+  if (forced || rev == 0) return rev;
+  return std::max<uint64_t>(rev, num_tables <= 256 ? 3000 : 65536);
+}
+
 RC FromStatus(int status) {
   if (status == ADL_OK) return OK;
   if (status == ADL_FILTER_BLOCK_ERROR) return FILTER_BLOCK_ERROR;
@@ -462,6 +490,105 @@ RC RevisionMultiGetFilter(FilterCache &cache, RevisionIndex &rev, const vector<s
   return OK;
 }
 
+namespace {
+
+/* group_level and level_begin of a plan whose group_table is set */
+void FillPlanLevels(const vector<uint32_t> &base, RevisionReadPlan &out) {
+  const size_t G = out.group_table.size(), L = base.size() - 1;
+  out.group_level.resize(G);
+  out.level_begin.assign(L + 1, 0);
+  for (size_t g = 0; g < G; ++g) {
+    const size_t l = std::upper_bound(base.begin(), base.end(), out.group_table[g]) - base.begin() - 1;
+    out.group_level[g] = (uint8_t)l;
+    ++out.level_begin[l + 1];
+  }
+  for (size_t l = 0; l < L; ++l) out.level_begin[l + 1] += out.level_begin[l];
+}
+
+}  // namespace
+
+void GroupHitsByTable(const RevisionMultiGetResult &hits, const vector<uint32_t> &table_base, RevisionReadPlan &out) {
+  out = RevisionReadPlan{};
+  out.uncached = hits.uncached;
+  const size_t K = hits.begin.empty() ? 0 : hits.begin.size() - 1, H = hits.table.size();
+  // a counting sort on the table id: the hits per table, the tables that have
+  // any (ascending) with their first entry, then the keys placed in batch order
+  vector<uint32_t> at(table_base.back() + 1, 0);
+  for (uint32_t t : hits.table) ++at[t + 1];
+  uint32_t run = 0;
+  for (size_t t = 0; t + 1 < at.size(); ++t) {
+    const uint32_t n = at[t + 1];
+    if (n) {
+      out.group_table.push_back((uint32_t)t);
+      out.group_begin.push_back(run);
+    }
+    at[t] = run;
+    run += n;
+  }
+  out.group_begin.push_back(run);
+  out.key.resize(H);
+  for (size_t i = 0; i < K; ++i)
+    for (uint32_t p = hits.begin[i]; p < hits.begin[i + 1]; ++p) out.key[at[hits.table[p]]++] = (uint32_t)i;
+  FillPlanLevels(table_base, out);
+}
+
+RC RevisionReadPlanFilter(FilterCache &cache, RevisionIndex &rev, const vector<string_view> &user_keys, int64_t seq,
+                          RevisionReadPlan &out) {
+  out = RevisionReadPlan{};
+  if (rev.status()) return rev.status();
+  const size_t K = user_keys.size(), L = rev.levels();
+  size_t live = 0;
+  for (size_t l = 0; l < L; ++l) live += rev.level(l) && rev.level(l)->tables();
+  const uint64_t min_keys = ReadPlanDeviceMinKeys(live, rev.table_base().back());
+  if (min_keys == 0 || K < min_keys) {
+    RevisionMultiGetResult hits;
+    if (RC rc = RevisionMultiGetFilter(cache, rev, user_keys, seq, hits)) return rc;
+    GroupHitsByTable(hits, rev.table_base(), out);
+    return OK;
+  }
+  adl_bloom_revision *h = rev.handle();
+  if (!h) return rev.device_status();
+  if (!cache.handle()) return cache.status();
+  size_t key_bytes = 0;
+  for (string_view k : user_keys) key_bytes += k.size();
+  KeyArena batch;
+  batch.Reserve(K, key_bytes);
+  for (string_view k : user_keys) batch.Add(k);
+  // Capacities as RevisionMultiGetFilter sizes them: twice the mean lists per
+  // key first, then the exact sizes the call reports.  No more groups than
+  // tables.
+  const uint64_t worst = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)K * rev.longest_list(), 0xffffffffull));
+  uint64_t mean = 0;
+  for (size_t l = 0; l < L; ++l)
+    if (rev.level(l) && rev.level(l)->tables()) mean += rev.level(l)->mean_list();
+  uint64_t pcap = std::min<uint64_t>(worst, 2ull * K * mean + 1024), ecap = pcap;
+  const uint64_t gcap = rev.table_base().back();
+  uint64_t np = 0, nh = 0, ng = 0;
+  int st = ADL_OK;
+  out.group_table.resize(gcap);
+  out.group_begin.resize(gcap + 1);
+  for (int attempt = 0; attempt < 3; ++attempt) {
+    out.key.resize(ecap);
+    st = adl_bloom_revision_read_plan(h, cache.handle(), 0, reinterpret_cast<const uint8_t *>(batch.bytes().data()),
+                                      batch.offsets().data(), K, 0, seq, out.group_table.data(),
+                                      out.group_begin.data(), gcap, &ng, out.key.data(), ecap, &nh, pcap, &np,
+                                      &out.uncached, nullptr);
+    if (st != ADL_ERR_WORKSPACE || np > worst) break;
+    if (np > pcap) pcap = np;
+    else if (nh > ecap) ecap = nh;
+    else break;
+  }
+  if (st != ADL_OK) {
+    out = RevisionReadPlan{};
+    return FromStatus(st);
+  }
+  out.group_table.resize(ng);
+  out.group_begin.resize(ng + 1);
+  out.key.resize(nh);
+  FillPlanLevels(rev.table_base(), out);
+  return OK;
+}
+
 }  // namespace adl
 
 namespace {
@@ -519,6 +646,29 @@ extern "C" int64_t adl_revision_index_candidates(const char *const *mins, const 
   std::vector<uint32_t> b, tb;
   rev.Candidates(HookKeys(keys, key_lens, 0, K), seq, b, tb);
   return HookResult(b, tb, begin, table, cap);
+}
+
+/* Test hook (tests/test_read_plan_cpu.py): GroupHitsByTable on a key-major
+ * result handed over as arrays (hit_begin: K+1 entries; table_base: L+1).
+ * group_table / group_level: up to group_cap entries, group_begin: one more;
+ * key: hit_begin[K] entries; level_begin: L+1.  Returns the number of groups,
+ * or -1 when group_cap is too small. */
+extern "C" int64_t adl_revision_group_hits(const uint32_t *hit_begin, const uint32_t *hit_table, uint32_t K,
+                                           const uint32_t *table_base, uint32_t L, uint32_t *group_table,
+                                           uint8_t *group_level, uint32_t *group_begin, uint64_t group_cap,
+                                           uint32_t *key, uint32_t *level_begin) {
+  adl::RevisionMultiGetResult hits;
+  hits.begin.assign(hit_begin, hit_begin + K + 1);
+  hits.table.assign(hit_table, hit_table + hit_begin[K]);
+  adl::RevisionReadPlan plan;
+  adl::GroupHitsByTable(hits, std::vector<uint32_t>(table_base, table_base + L + 1), plan);
+  if (plan.group_table.size() > group_cap) return -1;
+  std::copy(plan.group_table.begin(), plan.group_table.end(), group_table);
+  std::copy(plan.group_level.begin(), plan.group_level.end(), group_level);
+  std::copy(plan.group_begin.begin(), plan.group_begin.end(), group_begin);
+  std::copy(plan.key.begin(), plan.key.end(), key);
+  std::copy(plan.level_begin.begin(), plan.level_begin.end(), level_begin);
+  return (int64_t)plan.group_table.size();
 }
 
 /* Test hook (tests/test_level_cpu.py): LevelCandidates over tables and keys

@@ -203,4 +203,34 @@ struct RevisionMultiGetResult {
 RC RevisionMultiGetFilter(FilterCache &cache, RevisionIndex &rev, const vector<string_view> &user_keys, int64_t seq,
                           RevisionMultiGetResult &out);
 
+/* The hits of a revision multi-get table by table: what a reader that opens
+ * each table once works from.  Level::Get reads every candidate table of a
+ * level and keeps the smallest inner key (src/revision.cpp:279-308), so within
+ * a level each group is read whole; the levels are walked ascending
+ * (src/revision.cpp:391-403) and a key an earlier level has found is skipped
+ * in the later ones. */
+struct RevisionReadPlan {
+  vector<uint32_t> group_table; /* global ids of the tables with a hit, ascending */
+  vector<uint8_t> group_level;  /* the level of each, from table_base */
+  vector<uint32_t> group_begin; /* groups + 1 */
+  vector<uint32_t> key;         /* indices into user_keys; group g's are key[group_begin[g] .. group_begin[g+1]), ascending */
+  vector<uint32_t> level_begin; /* levels + 1: level l's groups are [level_begin[l], level_begin[l+1]) */
+  uint64_t uncached = 0;        /* entries whose table was not in the cache (answered 1) */
+};
+
+/* The plan of a key-major result (host only): a stable counting sort of the
+ * hits on the table id.  table_base: RevisionIndex::table_base(). */
+void GroupHitsByTable(const RevisionMultiGetResult &hits, const vector<uint32_t> &table_base, RevisionReadPlan &out);
+
+/* RevisionMultiGetFilter whose result comes back as a plan.  Small batches run
+ * it and then GroupHitsByTable; larger ones are ONE call
+ * (adl_bloom_revision_read_plan: keys up, the grouping on the device, the plan
+ * down).  Both give the same plan.  The threshold is RevisionMultiGetFilter's
+ * where the environment sets it (the same knobs; 0 = never the single call);
+ * otherwise that function's default or the measured floor, whichever is
+ * larger: 3 000 keys for revisions of up to 256 tables, 65 536 beyond
+ * ("Read plan"). */
+RC RevisionReadPlanFilter(FilterCache &cache, RevisionIndex &rev, const vector<string_view> &user_keys, int64_t seq,
+                          RevisionReadPlan &out);
+
 }  // namespace adl

@@ -119,4 +119,10 @@ __attribute__((visibility("hidden"))) int probe_fanout_hits_device(
     const uint8_t *d_k, uint32_t *d_hit_begin, uint32_t *d_hit_filter, uint64_t hit_capacity, uint64_t *d_num_hits,
     void *d_workspace, uint64_t workspace_bytes, hipStream_t st);
 
+// adl_bloom_hits_by_table_device on `st`, read_plan.hip.
+__attribute__((visibility("hidden"))) int hits_by_table_device(
+    const uint32_t *d_hit_begin, const uint32_t *d_hit_table, uint64_t num_keys, uint32_t num_tables,
+    uint32_t *d_group_table, uint32_t *d_group_begin, uint64_t group_capacity, uint32_t *d_entry_key,
+    uint64_t entry_capacity, uint64_t *d_counts, void *d_workspace, uint64_t workspace_bytes, hipStream_t st);
+
 }  // namespace adl_host

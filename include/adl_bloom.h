@@ -507,6 +507,63 @@ int adl_bloom_revision_multiget(adl_bloom_revision *rev, adl_bloom_filter_cache 
                                 uint64_t hit_capacity, uint64_t *num_hits, uint64_t pair_capacity,
                                 uint64_t *num_pairs, uint64_t *h_uncached, void *stream);
 
+/* The hits of a multi-get grouped by table, on the device.  Level::Get reads
+ * every candidate table of a level and keeps the smallest inner key
+ * (src/revision.cpp:279-308), so each hit within a level is a certain read,
+ * and each read opens its table's reader first (src/revision.cpp:289); a
+ * batched reader therefore wants the hits table by table.  Input: the output
+ * of adl_bloom_probe_fanout_hits_device -- d_hit_begin (num_keys+1 u32; H =
+ * d_hit_begin[num_keys] is read on the device) and d_hit_table, ids <
+ * num_tables, no id twice in one key's list.  Output: the G tables with at
+ * least one hit in d_group_table, ascending by id (for a revision's global
+ * ids: the levels ascending, src/revision.cpp:391-403); d_group_begin (G+1
+ * entries); d_entry_key[d_group_begin[g] .. d_group_begin[g+1]) the indices
+ * of the keys that hit d_group_table[g], ascending.  d_counts (two device
+ * u64): [0] = H, [1] = G, always written.  Entries from entry_capacity on and
+ * groups from group_capacity on (begins from group_capacity+1 on) are not
+ * written; with H > entry_capacity nothing is grouped and only d_counts[0]
+ * means anything.  Whatever the arrays hold (ids >= num_tables included),
+ * nothing outside the outputs and the workspace is written.  The output is
+ * deterministic (a stable radix sort on the id, 8 bits per pass, and a stable
+ * compaction: no atomic decides a position).  Stream-ordered with no
+ * synchronisation; four launches up to 256 tables, 4 + 3 *
+ * ceil(bits(num_tables-1) / 8) beyond, whatever the arrays hold; num_keys == 0
+ * launches none and reports 0 / 0.  ADL_ERR_TOO_LARGE: num_keys >= 2^32-1 or entry_capacity >=
+ * 2^32.  d_workspace: 256-byte aligned (else ADL_ERR_INVALID_ARG),
+ * adl_bloom_hits_by_table_workspace_bytes(num_keys, entry_capacity,
+ * num_tables) bytes (fewer: ADL_ERR_WORKSPACE; the size is 0 for an
+ * entry_capacity of 2^32 or more). */
+uint64_t adl_bloom_hits_by_table_workspace_bytes(uint64_t num_keys, uint64_t entry_capacity, uint32_t num_tables);
+int adl_bloom_hits_by_table_device(const uint32_t *d_hit_begin, const uint32_t *d_hit_table, uint64_t num_keys,
+                                   uint32_t num_tables, uint32_t *d_group_table, uint32_t *d_group_begin,
+                                   uint64_t group_capacity, uint32_t *d_entry_key, uint64_t entry_capacity,
+                                   uint64_t *d_counts, void *d_workspace, uint64_t workspace_bytes, void *stream);
+
+/* Revision multi-get that returns a read plan: adl_bloom_revision_multiget's
+ * work (same arguments, same resolution and pinning of the oids, same answers)
+ * followed by the grouping above, in one call.  h_group_table (*num_groups
+ * global ids, ascending: the levels ascending), h_group_begin (*num_groups+1)
+ * and h_entry_key (*num_hits key indices; group g's ascending) come back: the
+ * tables to open, and for each the batch's keys to look up in it, in batch
+ * order.  The reader walks the levels ascending (src/revision.cpp:391-403),
+ * within a level visits each group once (every table of the level that
+ * survives is read, src/revision.cpp:279-308) and skips the keys an earlier
+ * level has found.  The key-major hit lists stay on the device beside the
+ * candidate pairs, which pair_capacity sizes as for
+ * adl_bloom_revision_multiget: a pair total above it is ADL_ERR_WORKSPACE with
+ * *num_pairs set and nothing else written, one of 2^32 or more
+ * ADL_ERR_TOO_LARGE.  *num_hits > entry_capacity or *num_groups >
+ * group_capacity is ADL_ERR_WORKSPACE with both counts set (both exact) and
+ * no array written.  A level created without oids: ADL_ERR_INVALID_ARG.
+ * *h_uncached counts the entries whose table was not cached.  num_keys == 0
+ * launches nothing (h_group_begin[0] = 0).  Synchronous. */
+int adl_bloom_revision_read_plan(adl_bloom_revision *rev, adl_bloom_filter_cache *cache, uint32_t filter,
+                                 const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t num_keys,
+                                 uint32_t key_stride, int64_t seq, uint32_t *h_group_table, uint32_t *h_group_begin,
+                                 uint64_t group_capacity, uint64_t *num_groups, uint32_t *h_entry_key,
+                                 uint64_t entry_capacity, uint64_t *num_hits, uint64_t pair_capacity,
+                                 uint64_t *num_pairs, uint64_t *h_uncached, void *stream);
+
 /* ------------------------------------------- write-through builds into the cache */
 
 /* A table's filter block built straight into a reserved range of the cache
