@@ -564,6 +564,7 @@ def murmur3(seed: int, data: bytes) -> int:
 TEST_FAULT_PIPELINE_GROUP = 1
 TEST_FAULT_CACHE_COMPLETION = 2
 TEST_FAULT_CACHE_BUILD_CORRUPT = 3
+TEST_FAULT_SERVER_SEQ = 4  # no failure: presets the calling thread's next probe-server sequence number
 
 
 def test_fault(site: int, arg: int) -> None:
@@ -576,6 +577,16 @@ def probe_server_launches() -> int:
     n = ctypes.c_uint64(0)
     _check(lib().adl_bloom_probe_server_launches(ctypes.byref(n)), "adl_bloom_probe_server_launches")
     return n.value
+
+
+def probe_server_phases(reset: bool = False):
+    """(requests served by a resident probe server, of them stamped, avg_us[7]) since the last reset
+    (adl_bloom_probe_server_phases).  A request that fell back to a launched probe is not counted."""
+    n, st = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    avg = (ctypes.c_double * 7)()
+    _check(lib().adl_bloom_probe_server_phases(ctypes.byref(n), ctypes.byref(st), avg, int(reset)),
+           "adl_bloom_probe_server_phases")
+    return n.value, st.value, list(avg)
 
 
 def profile_enable(capacity: int = 4096) -> None:

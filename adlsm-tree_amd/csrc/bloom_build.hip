@@ -1796,6 +1796,10 @@ const char *adl_bloom_strerror(int status) {
 int adl_bloom_abi_version(void) { return ADL_BLOOM_ABI_VERSION; }
 
 int adl_bloom_test_fault(int site, int64_t arg) {
+  if (site == ADL_TEST_FAULT_SERVER_SEQ) {
+    adl_host::t_server_seq_preset = arg < 0 ? -1 : arg;
+    return ADL_OK;
+  }
   if (site != ADL_TEST_FAULT_PIPELINE_GROUP && site != ADL_TEST_FAULT_CACHE_COMPLETION &&
       site != ADL_TEST_FAULT_CACHE_BUILD_CORRUPT)
     return ADL_ERR_INVALID_ARG;

@@ -531,4 +531,10 @@ struct TestFaults {
 };
 inline TestFaults g_test_faults;
 
+// ADL_TEST_FAULT_SERVER_SEQ: the sequence number the calling thread's next
+// probe-server request continues its slot from (-1: none).  Per thread, since
+// a slot belongs to the thread that posts into it: a preset armed by one
+// thread is not taken by another thread's request.  probe_server.hip takes it.
+inline thread_local int64_t t_server_seq_preset = -1;
+
 }  // namespace adl_host

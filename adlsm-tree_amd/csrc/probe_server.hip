@@ -55,6 +55,18 @@
 // without a lock while DoCompaction runs, src/db.cpp:164-172, 263, 294).  The
 // server runs on a stream of its own at the highest priority, so no other
 // stream's work queues behind it on a shared hardware queue (Server::create).
+//
+// Tests.  Lifetime, relaunch, teardown, stale arena ranges and threads:
+// tests/test_gpu_readpath.py (test_probe_server_*, test_filter_cache_mixed_bpk,
+// test_gets_beside_builds).  The request itself -- every key length 0..320 as
+// a member and as a non-member, slots filled to exactly kMaxKeyBytes with keys
+// at every offset mod 8, the inline edge at kInlineKeyBytes, inline slots
+// against slot 4, slots shared by more threads than kSlots, every k around
+// kReads, the divisor classes of fastmod_for, and the wraps of the 24-bit
+// answer tag and of kSeqMask (ADL_TEST_FAULT_SERVER_SEQ presets a slot's
+// sequence): tests/test_gpu_probe_server_geometry.py over the case table of
+// tests/serverkeys.py, which tests/test_probe_server_cases_cpu.py holds to the
+// oracle without a GPU.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -788,8 +800,14 @@ int probe(Server *s, const uint8_t *h_keys, const uint64_t *h_offsets, uint32_t 
   }
   std::lock_guard<std::mutex> slot_guard(s->slot_mu[my]);
   fold_phases(s->host, my, s->last_bell[my], s->last_seen[my]);
-  // 31-bit sequence numbers, never 0 (the initial done); bit 31 of the bell
-  // value says where the request is
+  // 30-bit sequence numbers, never 0 (the initial done); bit 31 of the bell
+  // value says where the request is, bit 30 asks for an invalidate
+  if (adl_host::t_server_seq_preset >= 0) {
+    // adl_bloom_test_fault(ADL_TEST_FAULT_SERVER_SEQ): the tests start this
+    // thread's slot just below a wrap (2^24: the answer tag; 2^30: the bell)
+    s->seq[my] = (uint32_t)adl_host::t_server_seq_preset & kSeqMask;
+    adl_host::t_server_seq_preset = -1;
+  }
   s->seq[my] = (s->seq[my] + 1) & kSeqMask;
   if (s->seq[my] == 0) s->seq[my] = 1;
   const bool inl = my < kInlineSlots && n == 1 && key_bytes <= kInlineKeyBytes && range[1] >= range[0] &&

@@ -728,10 +728,21 @@ int adl_bloom_build_positions(const uint64_t *key_counts, uint32_t num_filters, 
  * build clears the first non-zero byte of filter 0's bitmap in its arena
  * range, after the build and before verification (corrupted data, nothing
  * faults): the only way to see ADL_BLOOM_CACHE_VERIFY reject a build.
- * arg < 0 disarms. */
+ * ADL_TEST_FAULT_SERVER_SEQ, arg v >= 0: no failure, a counter preset.  The
+ * calling thread's next request to a resident probe server (any cache's)
+ * continues its slot's sequence from v & 0x3FFFFFFF, as if that slot had
+ * served so many requests: the request carries v + 1, so the tests reach the
+ * answer tag's wrap at 2^24 and the sequence number's at 2^30 (which skips 0)
+ * without the minutes of Gets either takes.  Kept per thread (a slot belongs
+ * to the thread that posts into it) and taken once, by that thread's next
+ * served-path request only.  It stores the counter and nothing else.
+ * arg < 0 disarms.
+ * (ADL_TEST_FAULT_SERVER_SEQ was added without a new ADL_BLOOM_ABI_VERSION:
+ * the signature is unchanged and the value was rejected before.) */
 #define ADL_TEST_FAULT_PIPELINE_GROUP 1
 #define ADL_TEST_FAULT_CACHE_COMPLETION 2
 #define ADL_TEST_FAULT_CACHE_BUILD_CORRUPT 3
+#define ADL_TEST_FAULT_SERVER_SEQ 4
 int adl_bloom_test_fault(int site, int64_t arg);
 
 /* The tuning and test switches (ADL_BLOOM_* environment variables, DESIGN.md

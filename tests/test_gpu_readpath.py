@@ -342,7 +342,13 @@ def _pack(keys):
 def test_probe_server_single_keys_vs_oracle(dev, ab, oracle, knobs, bpk):
     """Batches of 1..8 queries (keys of 0..288 bytes, several tables, an
     uncached table, a filter index the block does not have) through the
-    resident server equal the oracle and the launched probe."""
+    resident server equal the oracle and the launched probe.
+
+    The requests are sampled at random: members are at most 64 bytes long (a
+    longer key is a non-member, which a wrong hash answers 0 as well), no
+    request exceeds 288 bytes, and the slot a thread gets is not chosen.  The
+    request geometry is tested on purpose in
+    tests/test_gpu_probe_server_geometry.py (case table: tests/serverkeys.py)."""
     T = 3
     tabs = [_varlen_block(oracle, 40 + t + bpk, 3000, bpk) for t in range(T)]
     cache = ab.FilterCache(16 << 20, max_tables=8, bits_per_key=bpk)
