@@ -522,9 +522,15 @@ def hits_by_table(hit_begin, hit_table, num_tables: int, entry_capacity: int | N
 def probe_batch(keys, filter_id, bitmaps, bitmap_off, offsets=None, bits_per_key: int = 10, stream=None,
                 bitmap_end=None, out=None):
     """Large-batch multi-filter probe (adl_bloom_probe_batch_device): the answers of
-    probe_multi, through the tile-binned pipeline when the batch is large.  The
-    workspace comes from torch's caching allocator.  `out`: an optional uint8
-    device tensor of at least n bytes (any alignment) to answer into."""
+    probe_multi, through the tile-binned pipeline when the batch is large: 16-byte
+    keys (an (n, 16) tensor at a 16-byte-aligned address) from 2^20 queries on;
+    variable-length keys (`offsets`, n + 1 uint64 from any base) and any other
+    stride, at any alignment, from ADL_BLOOM_PROBE_BATCH_VAR_MIN queries on (0:
+    never; include/adl_bloom.h).  Every other batch goes to the direct kernel
+    inside the call; the answers are the same.  The workspace (sized with
+    key_stride 0 for keys with offsets) comes from torch's caching allocator.
+    `out`: an optional uint8 device tensor of at least n bytes (any alignment)
+    to answer into."""
     pk, po, n, stride = _keyset(keys, offsets)
     F = bitmap_off.numel() - (0 if bitmap_end is not None else 1)
     L = lib()

@@ -191,6 +191,11 @@ __device__ __forceinline__ uint32_t block_excl_scan_array_1b(uint32_t *a, uint32
 
 namespace adl_host {
 
+// The measured crossover of the binned probe for keys that are not 16-byte
+// keys (profiles/probe_varlen/): slower than the direct kernel at
+// 2^20 queries, at least 18 % faster from 2^22 on.
+constexpr uint64_t kProbeBatchVarMinDefault = 1ull << 22;
+
 // Tuning and test switches, read from the environment once per
 // process.  adl_bloom_reload_knobs() reads them again (tests, between calls:
 // no call of the library may be running).
@@ -211,6 +216,11 @@ struct Knobs {
   uint32_t build_queues = 2;
   uint32_t build_queue_passes = 3;
   bool server_invalidate = false;  // ADL_BLOOM_SERVER_INVALIDATE: the server invalidates its caches at every request
+  // ADL_BLOOM_PROBE_BATCH_VAR_MIN: the smallest batch of keys that are not
+  // 16-byte keys (offsets, or a stride other than 16) that takes the binned
+  // probe pipeline (probe_binned.hip).  0: never; 1 .. 2^20 mean 2^20 (the
+  // pipeline's own floor).  Not set: kProbeBatchVarMinDefault.
+  uint64_t probe_batch_var_min = kProbeBatchVarMinDefault;
   bool debug = false;             // ADL_BLOOM_DEBUG: the plan and failing HIP calls to stderr
   uint32_t exp = 0, pb_exp = 0;   // ADL_BLOOM_EXP / ADL_PB_EXP: diagnostics build (make stamps) only
 
@@ -232,6 +242,8 @@ struct Knobs {
     build_queues = (uint32_t)u64("ADL_BLOOM_BUILD_QUEUES", 2);
     build_queue_passes = (uint32_t)u64("ADL_BLOOM_BUILD_QUEUE_PASSES", 3);
     server_invalidate = u64("ADL_BLOOM_SERVER_INVALIDATE", 0) != 0;
+    probe_batch_var_min = u64("ADL_BLOOM_PROBE_BATCH_VAR_MIN", kProbeBatchVarMinDefault);
+    if (probe_batch_var_min) probe_batch_var_min = std::max<uint64_t>(probe_batch_var_min, 1ull << 20);
     debug = u64("ADL_BLOOM_DEBUG", 0) != 0;
 #ifdef ADL_BLOOM_STAMPS
     exp = (uint32_t)u64("ADL_BLOOM_EXP", 0);

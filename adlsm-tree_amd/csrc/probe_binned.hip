@@ -19,6 +19,10 @@
 //   K2  per filter: its queries' start in filter order, its chunks of C
 //       queries and its (tile, chunk) table; and each block's starting slot
 //       in every filter's run
+//   KH  keys that are not aligned 16-byte keys only (variable length, any other
+//       stride): per run of 512 queries, both murmur hashes of every query,
+//       hashed from LDS in length order, stored at the query's index (8 B a
+//       query); K3 then reads the pairs instead of keys
 //   K3  per block: both murmur hashes of every query, counting-sorted by
 //       filter in LDS and written out run by run (whole lines) to the
 //       query's slot in filter order: the batch grouped by filter, 8 B a
@@ -83,11 +87,12 @@ struct Plan {
   // workspace byte offsets
   uint32_t ng = 0;  // groups of kScanGroup blocks (K2)
   uint64_t o_desc, o_scal, o_cnt, o_start, o_gsum, o_cf, o_dest, o_hs, o_ent, o_tab, o_split, o_res, total;
+  uint64_t o_qh = 0;  // the queries' hash pairs in query order (pb_hash_kernel); keys that are not 16-byte keys only
 };
 
 constexpr uint32_t kScanGroup = 64;  // blocks per column-sum group (K2)
 
-Plan make_plan(uint64_t n, uint32_t F, int32_t bpk) {
+Plan make_plan(uint64_t n, uint32_t F, int32_t bpk, bool pairs) {
   Plan p;
   p.n = n;
   p.F = F;
@@ -116,6 +121,7 @@ Plan make_plan(uint64_t n, uint32_t F, int32_t bpk) {
   p.o_tab = take(p.maxch * (kMaxTiles + 1) * 4);
   p.o_split = take((kMaxSlots + 1) * 4);
   p.o_res = take(n + 64);
+  if (pairs) p.o_qh = take(n * 8);  // last: every other array is where the 16-byte plan has it
   p.total = o;
   return p;
 }
@@ -352,10 +358,203 @@ __device__ __forceinline__ void load_runs(const uint32_t *cnt, const uint32_t *s
   block_excl_scan_array<BLK>(lbase, F + 1, scratch);
 }
 
+// ---------------------------------------------------------------- KH
+// Both hashes of every query whose keys are not aligned 16-byte keys
+// (variable length, or a fixed stride other than 16, at any alignment), to
+// qh[i] at the query's own index i; K3 then takes the pairs instead of keys.
+// One workgroup per run of S consecutive queries:
+//   load   the run's offsets and its key bytes -- whole 16-byte blocks of
+//          memory from the block holding the run's first byte, up to kStage
+//          bytes -- all requested before the first is used (clamped indices);
+//   sort   the keys counted into kPhBins exact-length bins in LDS, each key's
+//          (start, length, index in the run) scattered to its sorted slot, so
+//          that the 64 keys a wave hashes in lockstep are about equally long;
+//   hash   wave w takes groups of 64 sorted slots, longest first, each lane one
+//          key from LDS (hash_lds); a key past the staged bytes, one of 64 KiB
+//          or more, or one 4 GiB or more past the run's first block is hashed
+//          from global memory (hash_bytes);
+//   out    qh[first query of the run + index in the run] = (h1, h2).
+// (The run staging is like the build's hash_var_kernel, bloom_build.hip, whose
+// output order and alignment contract differ; the likeness is accepted.)
+//
+// Read contract (include/adl_bloom.h: any alignment, no byte outside a key is
+// read): the batch's keys are the byte range [keys + off(0), keys + off(n)).
+// A staged 16-byte block that lies inside that range holds only bytes of this
+// batch's keys and is loaded whole.  The block the range starts in and the one
+// it ends in may reach outside it: of those two only the bytes inside the
+// range are loaded, one at a time (`edge` below).  A run of empty keys loads
+// nothing.  hash_bytes reads a key's own bytes only.
+constexpr int kPhBlk = 256;
+constexpr uint32_t kPhRun = 512;   // queries per run (the build's measured shape)
+constexpr uint32_t kPhBins = 512;  // exact key length 0..510; 511 = longer
+
+struct QVar {  // key i = keys[offs[i] .. offs[i+1])
+  const uint8_t *keys;
+  const uint64_t *offs;
+  __device__ __forceinline__ uint64_t off(uint64_t i) const { return offs[i]; }
+};
+
+struct QStride {  // key i = keys[i * stride .. (i+1) * stride)
+  const uint8_t *keys;
+  uint32_t stride;
+  __device__ __forceinline__ uint64_t off(uint64_t i) const { return i * stride; }
+};
+
+template <uint32_t S>
+constexpr uint32_t ph_stage_bytes() {
+  return S * 48;  // LDS staging of a run's key bytes (mean var-len key ~40 B)
+}
+
+template <uint32_t S>
+constexpr size_t ph_lds_bytes() {
+  return kPhBins * 4 + S * 4 + S * 2 + S * 2 + ph_stage_bytes<S>() + 16;  // + hash_lds's read slack
+}
+
+template <uint32_t S, class Keys>
+__global__ __launch_bounds__(kPhBlk) void pb_hash_kernel(Keys keys, uint64_t n, uint2 *__restrict__ qh) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  uint32_t *bins = lds;                                        // kPhBins
+  uint32_t *s_rel = lds + kPhBins;                             // key start - base16, by sorted slot
+  uint16_t *s_len = reinterpret_cast<uint16_t *>(s_rel + S);   // length (0xffff: hashed from global memory)
+  uint16_t *s_idx = s_len + S;                                 // index in the run
+  uint32_t *stage = reinterpret_cast<uint32_t *>(s_idx + S);   // 16-byte aligned (S % 4 == 0)
+  static_assert(S % kPhBlk == 0 && S <= 512, "whole rounds of keys per thread; the rank fits 9 bits");
+  constexpr int KPT = S / kPhBlk;
+  constexpr uint32_t NW = kPhBlk / kWave;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const uint64_t q0 = (uint64_t)blockIdx.x * S;  // (the grid is ceil(n / S): q0 < n)
+  const uint32_t cnt = (uint32_t)min((uint64_t)S, n - q0);
+  const uint64_t kaddr = reinterpret_cast<uintptr_t>(keys.keys);
+  // addresses: the batch's byte range, the run's, and the run's first block
+  const uint64_t lo = kaddr + keys.off(0), hi = kaddr + keys.off(n);
+  const uint64_t rb = kaddr + keys.off(q0), re = kaddr + keys.off(q0 + cnt);
+  const uint64_t base16 = rb & ~15ull;
+  constexpr uint32_t kStage = ph_stage_bytes<S>();
+  static_assert(kStage % (16 * kPhBlk) == 0, "the staging loads cover kStage in whole rounds of 16 B per thread");
+  // staged: bytes [base16, base16 + 16 * nv), each block holding a byte of the run
+  const uint32_t nv = re > rb ? (uint32_t)(min((re - base16 + 15) & ~15ull, (uint64_t)kStage) / 16) : 0u;
+  const uint32_t sbytes = nv * 16;
+  // blocks [vb, ve) lie inside the batch's range; block 0 and block nv - 1 may not
+  const uint32_t vb = base16 < lo ? 1u : 0u;
+  const uint32_t ve = (nv && base16 + 16ull * nv > hi) ? nv - 1u : nv;
+
+  constexpr int VPT = kStage / 16 / kPhBlk;
+  for (uint32_t i = tid; i < kPhBins; i += kPhBlk) bins[i] = 0;
+  uint64_t o0[KPT], o1[KPT];
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    const uint32_t idx = min((uint32_t)(tid + i * kPhBlk), cnt - 1u);
+    o0[i] = keys.off(q0 + idx);
+    o1[i] = keys.off(q0 + idx + 1);
+  }
+  u32x4_t v[VPT];  // (the ext-vector type: an array of uint4 held across the barrier goes to scratch)
+  if (vb < ve) {
+    const u32x4_t *src = reinterpret_cast<const u32x4_t *>(base16);
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) v[i] = src[min(max((uint32_t)(tid + i * kPhBlk), vb), ve - 1u)];
+  }
+  // edge: threads 0..15 take the bytes of block 0, threads 16..31 those of
+  // block nv - 1, where that block is not loaded whole; only bytes inside the
+  // batch's range
+  uint32_t edge_at = ~0u, edge_byte = 0;
+  if (tid < 32 && nv) {
+    const uint32_t blk = tid < 16 ? 0u : nv - 1u;
+    const bool partial = tid < 16 ? vb != 0u : (ve < nv && !(nv == 1u && vb != 0u));
+    const uint64_t a = base16 + 16ull * blk + (tid & 15);
+    if (partial && a >= lo && a < hi) {
+      edge_at = 16u * blk + (tid & 15);
+      edge_byte = *reinterpret_cast<const uint8_t *>(a);
+    }
+  }
+  __syncthreads();
+  // ---- sort the run's keys by length
+  uint32_t rk[KPT];
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    rk[i] = ~0u;
+    if (tid + i * kPhBlk < cnt) {
+      const uint32_t c = (uint32_t)min(o1[i] - o0[i], (uint64_t)(kPhBins - 1));
+      rk[i] = (atomicAdd(&bins[c], 1u) << 9) | c;
+    }
+  }
+  {
+    u32x4_t *dst = reinterpret_cast<u32x4_t *>(stage);
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+      const uint32_t j = tid + i * kPhBlk;
+      if (j >= vb && j < ve) dst[j] = v[i];
+    }
+    if (edge_at != ~0u) reinterpret_cast<uint8_t *>(stage)[edge_at] = (uint8_t)edge_byte;
+  }
+  __syncthreads();
+  if (wave == 0) {  // exclusive scan of the bins, 8 per lane
+    constexpr int PER = kPhBins / kWave;
+    uint32_t bv[PER], t = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) bv[j] = bins[lane * PER + j], t += bv[j];
+    uint32_t run = wave_incl_scan(t, lane) - t;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) bins[lane * PER + j] = run, run += bv[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) {
+    if (rk[i] != ~0u) {
+      const uint32_t slot = bins[rk[i] & (kPhBins - 1)] + (rk[i] >> 9);
+      const uint64_t len = o1[i] - o0[i], rel = kaddr + o0[i] - base16;
+      // a key of 64 KiB or more, or one starting 4 GiB or more past the run's
+      // first block, is found again by its index (and hashed from global memory)
+      const bool near = len < 0xffffu && rel < 0xffffffffull;
+      s_rel[slot] = near ? (uint32_t)rel : 0u;
+      s_len[slot] = near ? (uint16_t)len : (uint16_t)0xffffu;
+      s_idx[slot] = (uint16_t)(tid + i * kPhBlk);
+    }
+  }
+  __syncthreads();
+  // ---- hash, group g = 64 sorted slots; longest groups first (slots are
+  // sorted by length): the waves start on the groups that set the workgroup's end
+  const uint32_t groups = (cnt + kWave - 1) / kWave;
+  for (uint32_t gi = wave; gi < groups; gi += NW) {
+    const uint32_t s = (groups - 1 - gi) * kWave + lane;
+    if (s >= cnt) continue;
+    uint32_t len = s_len[s];
+    const uint32_t r = s_rel[s], ix = s_idx[s];
+    uint32_t h1, h2;
+    if (len < 0xffffu && (uint64_t)r + len <= sbytes) {
+      hash_lds(stage, r, len, h1, h2);
+    } else {
+      const uint8_t *p = reinterpret_cast<const uint8_t *>(base16 + r);
+      if (len == 0xffffu) {
+        const uint64_t k0 = keys.off(q0 + ix);
+        len = (uint32_t)(keys.off(q0 + ix + 1) - k0);
+        p = keys.keys + k0;
+      }
+      hash_bytes(p, len, kSeed1, kSeed2, h1, h2);
+    }
+    qh[q0 + ix] = make_uint2(h1, h2);
+  }
+}
+
 // ---------------------------------------------------------------- K3
-__global__ __launch_bounds__(kBlk) void pb_scatter_kernel(const uint4 *__restrict__ keys,
-                                                          const uint32_t *__restrict__ fid, uint64_t n, uint32_t F,
-                                                          uint32_t nb, const PFilter *__restrict__ desc,
+// What K3 takes per query: the 16-byte key itself (hashed here), or the
+// (h1, h2) pair pb_hash_kernel left at the query's index.
+struct SrcKeys16 {
+  const uint4 *keys;
+  using Raw = uint4;
+  __device__ __forceinline__ Raw load(uint64_t i) const { return load_nt(keys + i); }
+  __device__ __forceinline__ static void hash(const Raw &k, uint32_t &h1, uint32_t &h2) { hash16(k, h1, h2); }
+};
+
+struct SrcPairs {
+  const uint2 *qh;
+  using Raw = uint2;
+  __device__ __forceinline__ Raw load(uint64_t i) const { return qh[i]; }
+  __device__ __forceinline__ static void hash(const Raw &k, uint32_t &h1, uint32_t &h2) { h1 = k.x, h2 = k.y; }
+};
+
+template <class Src>
+__global__ __launch_bounds__(kBlk) void pb_scatter_kernel(Src src, const uint32_t *__restrict__ fid, uint64_t n,
+                                                          uint32_t F, uint32_t nb, const PFilter *__restrict__ desc,
                                                           const uint32_t *__restrict__ cnt,
                                                           const uint32_t *__restrict__ start,
                                                           uint16_t *__restrict__ dest, uint2 *__restrict__ hs,
@@ -374,12 +573,12 @@ __global__ __launch_bounds__(kBlk) void pb_scatter_kernel(const uint4 *__restric
   const uint32_t blk = xcd_block(nb);
   const uint64_t i0 = (uint64_t)blk * kQB + tid;
   uint32_t fq[kQPT];
-  uint4 kq[kQPT];
+  typename Src::Raw kq[kQPT];
 #pragma unroll
   for (uint32_t r = 0; r < kQPT; ++r) {
     const uint64_t i = min(i0 + (uint64_t)r * kBlk, n - 1);
     fq[r] = fid[i];
-    kq[r] = load_nt(keys + i);
+    kq[r] = src.load(i);
   }
   load_runs(cnt, start, blk, F, desc, lcnt, lstart, lbase, ltiles, scratch);
   for (uint32_t f = tid; f <= F; f += kBlk) lcur[f] = lbase[f];
@@ -397,7 +596,7 @@ __global__ __launch_bounds__(kBlk) void pb_scatter_kernel(const uint4 *__restric
           h1 = kq[r].x;
           h2 = kq[r].y;
         } else {
-          hash16(kq[r], h1, h2);
+          Src::hash(kq[r], h1, h2);
         }
         lhs[place] = make_uint2(h1, h2);
       }
@@ -931,10 +1130,19 @@ __global__ __launch_bounds__(kGatherBlk) void pb_gather_kernel(const uint16_t *_
   }
 }
 
-bool eligible(uint64_t n, uint32_t F, uint32_t key_stride, const uint8_t *d_keys, const uint64_t *d_offsets) {
-  return !d_offsets && key_stride == 16 && reinterpret_cast<uintptr_t>(d_keys) % 16 == 0 && n >= kMinBinned &&
-         n < 0x7fffffffull && F >= 1 && F <= kMaxBucketFilters;
+// The key shape of a batch: aligned 16-byte keys are hashed inside K3; the
+// other two go through pb_hash_kernel first.
+enum class Shape { kKeys16, kVar, kStride };
+
+bool filters_and_size_ok(uint64_t n, uint32_t F) { return n < 0x7fffffffull && F >= 1 && F <= kMaxBucketFilters; }
+
+// Keys that are not 16-byte keys take the pipeline from ADL_BLOOM_PROBE_BATCH_VAR_MIN queries on (0: never).
+bool var_eligible(uint64_t n, uint32_t F) {
+  const uint64_t vmin = adl_host::knobs().probe_batch_var_min;
+  return vmin && n >= vmin && filters_and_size_ok(n, F);
 }
+
+bool keys16_eligible(uint64_t n, uint32_t F) { return n >= kMinBinned && filters_and_size_ok(n, F); }
 
 }  // namespace
 
@@ -943,10 +1151,10 @@ extern "C" {
 uint64_t adl_bloom_probe_batch_workspace_bytes(uint64_t n, uint32_t num_filters, int32_t bits_per_key,
                                                uint32_t key_stride) {
   if (bits_per_key < 0) return 0;
-  if (key_stride != 16 || n < kMinBinned || n >= 0x7fffffffull || num_filters == 0 ||
-      num_filters > kMaxBucketFilters)
+  const bool k16 = key_stride == 16;  // (an unaligned pointer is not seen here: such a batch needs no more than this)
+  if (!(k16 ? keys16_eligible(n, num_filters) : var_eligible(n, num_filters)))
     return 256;  // the direct kernel: no workspace
-  return make_plan(n, num_filters, bits_per_key).total + 256;
+  return make_plan(n, num_filters, bits_per_key, !k16).total + 256;
 }
 
 int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n, uint32_t key_stride,
@@ -957,14 +1165,30 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
   if (!d_keys || !d_filter_id || !d_out || bits_per_key < 0) return ADL_ERR_INVALID_ARG;
   if (num_filters && (!d_bitmaps || !d_bitmap_off)) return ADL_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (!eligible(n, num_filters, key_stride, d_keys, d_offsets)) {
+  const Shape shape = d_offsets ? Shape::kVar : key_stride == 16 ? Shape::kKeys16 : Shape::kStride;
+  bool binned;
+  if (shape == Shape::kKeys16)  // 16-byte keys at an unaligned pointer stay direct (the workspace size cannot depend on it)
+    binned = reinterpret_cast<uintptr_t>(d_keys) % 16 == 0 && keys16_eligible(n, num_filters);
+  else
+    binned = (shape == Shape::kVar || key_stride != 0) && var_eligible(n, num_filters);
+  const uint32_t k_dbg = (uint32_t)adl_host::num_probes(bits_per_key);
+  if (adl_host::knobs().debug) {
+    char what[32];
+    if (shape == Shape::kStride || (shape == Shape::kKeys16 && !binned))
+      snprintf(what, sizeof what, "stride %u", key_stride);
+    else
+      snprintf(what, sizeof what, "%s", shape == Shape::kVar ? "var" : "keys16");
+    fprintf(stderr, "adl_bloom probe_batch: %s (%s), k=%u, launches=%d\n", binned ? "binned" : "direct", what, k_dbg,
+            binned ? (shape == Shape::kKeys16 ? 9 : 10) : 1);
+  }
+  if (!binned) {
     if (d_bitmap_end)
       return adl_bloom_probe_ranges_device(d_keys, d_offsets, n, key_stride, d_filter_id, num_filters, d_bitmaps,
                                            d_bitmap_off, d_bitmap_end, bits_per_key, d_out, stream);
     return adl_bloom_probe_multi_device(d_keys, d_offsets, n, key_stride, d_filter_id, num_filters, d_bitmaps,
                                         d_bitmap_off, bits_per_key, d_out, stream);
   }
-  const Plan p = make_plan(n, num_filters, bits_per_key);
+  const Plan p = make_plan(n, num_filters, bits_per_key, shape != Shape::kKeys16);
   if (!d_workspace || workspace_bytes < p.total + 256) return ADL_ERR_WORKSPACE;
   uint8_t *ws = reinterpret_cast<uint8_t *>(adl_host::round_up(reinterpret_cast<uintptr_t>(d_workspace), 256));
   PFilter *desc = reinterpret_cast<PFilter *>(ws + p.o_desc);
@@ -978,6 +1202,7 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
   uint32_t *tab = reinterpret_cast<uint32_t *>(ws + p.o_tab);
   uint8_t *res = ws + p.o_res;
   uint32_t *split = reinterpret_cast<uint32_t *>(ws + p.o_split);
+  uint2 *qh = reinterpret_cast<uint2 *>(ws + p.o_qh);  // (the new shapes only)
   const uint32_t F = num_filters;
   const uint32_t cus = adl_host::device_cus();
   const uint32_t g_tile = std::min(cus, kMaxSlots);  // pb_tile's workgroups
@@ -1005,10 +1230,26 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
     ADL_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(pb_starts_kernel, dim3(p.ng), dim3(kBlk), 0, st, cnt, gsum, p.nb, F, desc, start);
     ADL_HIP_TRY(hipGetLastError());
-    if (int rc = adl_host::lds_limit<pb_scatter_kernel>()) return rc;
-    hipLaunchKernelGGL(pb_scatter_kernel, dim3(p.nb), dim3(kBlk), lds_k3, st, reinterpret_cast<const uint4 *>(d_keys),
-                       d_filter_id, n, F, p.nb, desc, cnt, start, dest, hs, exp);
-    ADL_HIP_TRY(hipGetLastError());
+    if (shape == Shape::kKeys16) {
+      if (int rc = adl_host::lds_limit<pb_scatter_kernel<SrcKeys16>>()) return rc;
+      hipLaunchKernelGGL(pb_scatter_kernel<SrcKeys16>, dim3(p.nb), dim3(kBlk), lds_k3, st,
+                         SrcKeys16{reinterpret_cast<const uint4 *>(d_keys)}, d_filter_id, n, F, p.nb, desc, cnt, start,
+                         dest, hs, exp);
+      ADL_HIP_TRY(hipGetLastError());
+    } else {
+      const dim3 runs((uint32_t)((n + kPhRun - 1) / kPhRun));
+      if (shape == Shape::kVar)
+        hipLaunchKernelGGL((pb_hash_kernel<kPhRun, QVar>), runs, dim3(kPhBlk), ph_lds_bytes<kPhRun>(), st,
+                           QVar{d_keys, d_offsets}, n, qh);
+      else
+        hipLaunchKernelGGL((pb_hash_kernel<kPhRun, QStride>), runs, dim3(kPhBlk), ph_lds_bytes<kPhRun>(), st,
+                           QStride{d_keys, key_stride}, n, qh);
+      ADL_HIP_TRY(hipGetLastError());
+      if (int rc = adl_host::lds_limit<pb_scatter_kernel<SrcPairs>>()) return rc;
+      hipLaunchKernelGGL(pb_scatter_kernel<SrcPairs>, dim3(p.nb), dim3(kBlk), lds_k3, st, SrcPairs{qh}, d_filter_id, n,
+                         F, p.nb, desc, cnt, start, dest, hs, exp);
+      ADL_HIP_TRY(hipGetLastError());
+    }
     if (int rc = adl_host::lds_limit<pb_tile_kernel>()) return rc;
     auto bin = [&](auto lim, auto kern) -> int {
       if (int rc = lim()) return rc;

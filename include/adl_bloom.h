@@ -227,13 +227,34 @@ int adl_bloom_probe_fanout_device(const uint8_t *d_keys, const uint64_t *d_offse
 
 /* Large-batch probe with a workspace: the answers of adl_bloom_probe_multi_device
  * (d_bitmap_end == NULL) or adl_bloom_probe_ranges_device (filter f =
- * d_bitmaps[d_bitmap_off[f] .. d_bitmap_end[f])).  For big batches of 16-byte
- * keys over up to 4096 filters (n >= 2^20) it runs the tile-binned pipeline
- * (queries grouped by filter, positions sorted by 2^20-bit tile, bits tested
- * in LDS: streaming traffic instead of random bitmap reads);
- * otherwise the direct kernel.  A filter of 0 bytes or of 2^31 bits or more
- * answers 0.  Replaces BloomFilter::IsKeyExists (src/filter_block.cpp:49-62)
- * over a multi-get batch.  d_workspace: 256-byte aligned,
+ * d_bitmaps[d_bitmap_off[f] .. d_bitmap_end[f])).  For big batches over 1 to
+ * 4096 filters (n < 2^31 - 1) it runs the tile-binned pipeline (queries
+ * grouped by filter, positions sorted by 2^20-bit tile, bits tested in LDS:
+ * streaming traffic instead of random bitmap reads); otherwise
+ * the direct kernel.  The answers are the same bit for bit.  Which batches
+ * take the pipeline:
+ *   - 16-byte keys (d_offsets == NULL, key_stride == 16) at a 16-byte-aligned
+ *     d_keys, from n = 2^20 on.  16-byte keys at an unaligned pointer stay on
+ *     the direct kernel: the workspace size cannot depend on the pointer, and
+ *     its answer for key_stride == 16 is the aligned plan's.
+ *   - variable-length keys (d_offsets != NULL: n + 1 offsets from any base)
+ *     and any other fixed stride, at any alignment, from
+ *     ADL_BLOOM_PROBE_BATCH_VAR_MIN queries on (an environment switch, read
+ *     again by adl_bloom_reload_knobs: 0 never, 1 .. 2^20 mean 2^20; not set:
+ *     the measured crossover).  Their keys are hashed
+ *     first, in runs of 512 staged in LDS and sorted by length, into n * 8
+ *     more bytes of workspace.
+ * adl_bloom_probe_batch_workspace_bytes takes key_stride == 0 for
+ * variable-length keys (what a caller with d_offsets passes) and returns 256
+ * for a batch that stays on the direct kernel.  A batch that takes the
+ * pipeline with less workspace than that returns ADL_ERR_WORKSPACE.
+ * Read contract, as for every probe: d_keys at any alignment, and no byte
+ * outside [d_keys + off(0), d_keys + off(n)) is read -- the hashing kernel
+ * stages whole aligned 16-byte blocks only where they lie inside that range,
+ * and reads the two blocks the range starts and ends in byte by byte.
+ * A filter of 0 bytes or of 2^31 bits or more answers 0.  Replaces
+ * BloomFilter::IsKeyExists (src/filter_block.cpp:49-62) over a multi-get
+ * batch.  d_workspace: 256-byte aligned,
  * adl_bloom_probe_batch_workspace_bytes(n, num_filters, bpk, key_stride) bytes. */
 uint64_t adl_bloom_probe_batch_workspace_bytes(uint64_t n, uint32_t num_filters, int32_t bits_per_key,
                                                uint32_t key_stride);
