@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "bloom_common.hpp"
+#include "hash_run.hpp"
 #include "probe_server.hpp"
 
 using namespace adl_dev;
@@ -258,10 +259,23 @@ __device__ uint64_t g_stamps[3][2048][8];  // pass A, pass B, hashing pass
     if (threadIdx.x == 0 && blockIdx.x < 2048)                                    \
       for (int i_ = 0; i_ < 8; ++i_) g_stamps[pass][blockIdx.x][i_] = st_acc_[i_]; \
   } while (0)
+// hash_run's hook: STAMP(i) after phase i; exp & 16: no hashing (wrong pairs)
+struct StampHook {
+  uint64_t *acc, *t;
+  bool skip;
+  __device__ __forceinline__ void operator()(int i) const {
+    const uint64_t t_ = __builtin_amdgcn_s_memtime();
+    acc[i] += t_ - *t;
+    *t = t_;
+  }
+  __device__ __forceinline__ bool no_hash() const { return skip; }
+};
+#define STAMP_HOOK(a) StampHook{st_acc_, &st_t_, ((a).exp & 16) != 0}
 #else
 #define STAMP_DECL
 #define STAMP(i) do { } while (0)
 #define STAMP_FLUSH(pass) do { } while (0)
+#define STAMP_HOOK(a) RunNoHook{}
 #endif
 
 // ---------------------------------------------------------------- pass A
@@ -574,170 +588,37 @@ __global__ __launch_bounds__(BLOCK) kPassARegs void bloom_bin_kernel(BuildArgs a
 }
 
 // ---------------------------------------------------------------- var-len hashing
-// Variable-length keys (Zipf lengths) hashed before pass A, in length order.
-// A wave hashes 64 keys in lockstep, so it costs as much as its longest key;
-// keys sorted by exact length within runs of S keys give waves of nearly
-// equal keys.  One workgroup per run of a filter:
-//   sort   key lengths counted into kHvBins exact-length bins in LDS, each
-//          key's (start, length) scattered to its sorted slot;
-//   stage  the run's key bytes copied into LDS with coalesced 16-byte loads
-//          (each byte read from HBM once, in memory order);
-//   hash   wave w takes groups of 64 sorted slots, each lane one key, hashed
-//          from LDS (hash_lds: both seeds, alignbyte words); a key that lies
-//          past the staging buffer is hashed from global memory;
-//   out    (h1, h2) of sorted slot s to hp[chunk_base * C + first + s].
-// The bitmap is an OR over the filter's keys, so pass A may take them in this
-// order.  Pass A then reads 8 bytes per key (bloom_bin16_kernel over SrcH).
-// Workgroups are small (256 threads), two per CU, so one workgroup's sort and
-// staging overlap the other's hashing; no barrier waits for the slowest group
-// (a workgroup ends when its last wave does).
-// Measured against hashing in sorted order straight from global memory (lanes
-// reading scattered keys): L2 missed each key line ~3.7 times, 1.4 GB fetched
-// for 0.4 GB of keys.
+// Variable-length keys (Zipf lengths) hashed before pass A: one workgroup per
+// run of S keys of a filter, hashed from LDS in length order (hash_run.hpp).
+// (h1, h2) of sorted slot s goes to hp[chunk_base * C + first + s]: the bitmap
+// is an OR over the filter's keys, so pass A may take them in this order.
+// Pass A then reads 8 bytes per key (bloom_bin16_kernel over SrcH).
+// The key buffer is 16-byte aligned and may be read up to 15 bytes past the
+// run's last key (ReadWholeBlocks; include/adl_bloom.h).
 #ifndef ADL_HV_BLOCK
 #define ADL_HV_BLOCK 256
 #endif
 constexpr int kHvBlock = ADL_HV_BLOCK;
-constexpr uint32_t kHvBins = 512;          // exact key length 0..510; 511 = longer
-// LDS staging of a run's key bytes: 48 bytes per key (mean key ~40 B)
-template <uint32_t S>
-constexpr uint32_t hv_stage_bytes() {
-  return S * 48;
-}
 
-template <uint32_t S>
-constexpr size_t hv_lds_bytes() {
-  return kHvBins * 4 + S * 4 + S * 2 + hv_stage_bytes<S>() + 16;  // + hash_lds's read slack
-}
+struct HvOut {  // at the sorted slot
+  uint2 *out;
+  static constexpr bool kByIndex = false;
+  __device__ __forceinline__ void operator()(uint32_t s, uint32_t, uint32_t h1, uint32_t h2) const {
+    out[s] = make_uint2(h1, h2);
+  }
+};
 
 template <uint32_t S, bool DT>
 __global__ __launch_bounds__(kHvBlock) void hash_var_kernel(BuildArgs a, KeysVar keys, uint2 *__restrict__ hp,
                                                             uint32_t total_sc, FilterTable ft) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  uint32_t *bins = lds;                                             // kHvBins
-  uint32_t *s_rel = lds + kHvBins;                                  // key start - base16, by sorted slot
-  uint16_t *s_len = reinterpret_cast<uint16_t *>(s_rel + S);        // length (0xffff: >= 64 KiB)
-  uint32_t *stage = reinterpret_cast<uint32_t *>(s_len + S);        // 16-byte aligned (S % 8 == 0)
-  constexpr int KPT = S / kHvBlock;
-  constexpr uint32_t NW = kHvBlock / kWave;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const uint32_t sc = blockIdx.x;
   if (sc >= total_sc) return;
   STAMP_DECL
   const auto &d = Filt<DT>::at(a, ft, Filt<DT>::of_run(a, ft, sc));
   const uint32_t first = (sc - d.sc_base) * S;
   const uint32_t cnt = min(S, d.n - first);
-  const uint64_t kb = d.key_begin + first;
-  const uint64_t base16 = keys.offs[kb] & ~15ull;
-  const uint64_t end = keys.offs[kb + cnt];
-  // staged: bytes [base16, base16 + sbytes), whole 16-byte blocks of the
-  // (16-byte-aligned) key buffer, each holding at least one byte of the run:
-  // up to 15 bytes past the run's last key are read, never a block the key
-  // bytes do not touch (include/adl_bloom.h)
-  constexpr uint32_t kStage = hv_stage_bytes<S>();
-  static_assert(kStage % (16 * kHvBlock) == 0, "the staging loads cover kStage in whole rounds of 16 B per thread");
-  const uint32_t sbytes = (uint32_t)min((end - base16 + 15) & ~15ull, (uint64_t)kStage);
-
-  // ---- load the run's offsets and key bytes: every load in flight before
-  // the first is used (clamped indices: unconditional, countable waits), so
-  // the run costs one memory round trip
-  constexpr int VPT = kStage / 16 / kHvBlock;
-  const uint32_t nv = sbytes / 16;
-  for (uint32_t i = tid; i < kHvBins; i += kHvBlock) bins[i] = 0;
-  uint64_t o0[KPT], o1[KPT];
-#pragma unroll
-  for (int i = 0; i < KPT; ++i) {
-    const uint32_t idx = min((uint32_t)(tid + i * kHvBlock), cnt - 1u);
-    o0[i] = keys.offs[kb + idx];
-    o1[i] = keys.offs[kb + idx + 1];
-  }
-  u32x4_t v[VPT];  // (the ext-vector type: an array of uint4 held across the barrier goes to scratch)
-  if (nv) {  // a run of empty keys has no byte to stage (and maybe none to read)
-    const u32x4_t *src = reinterpret_cast<const u32x4_t *>(keys.keys + base16);
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) v[i] = src[min((uint32_t)(tid + i * kHvBlock), nv - 1u)];
-  }
-  __syncthreads();
-  STAMP(0);  // offsets and key bytes loaded
-  // ---- sort the run's keys by length
-  uint32_t rk[KPT];
-#pragma unroll
-  for (int i = 0; i < KPT; ++i) {
-    rk[i] = ~0u;
-    if (tid + i * kHvBlock < cnt) {
-      const uint32_t c = (uint32_t)min(o1[i] - o0[i], (uint64_t)(kHvBins - 1));
-      rk[i] = (atomicAdd(&bins[c], 1u) << 9) | c;
-    }
-  }
-  {
-    u32x4_t *dst = reinterpret_cast<u32x4_t *>(stage);
-#pragma unroll
-    for (int i = 0; i < VPT; ++i)
-      if (tid + i * kHvBlock < nv) dst[tid + i * kHvBlock] = v[i];
-  }
-  __syncthreads();
-  STAMP(1);  // lengths counted, bytes staged
-  if (wave == 0) {  // exclusive scan of the bins, 8 per lane
-    constexpr int PER = kHvBins / kWave;
-    uint32_t bv[PER], t = 0;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) bv[j] = bins[lane * PER + j], t += bv[j];
-    uint32_t run = wave_incl_scan(t, lane) - t;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) bins[lane * PER + j] = run, run += bv[j];
-  }
-  __syncthreads();
-  STAMP(2);  // bins scanned
-#pragma unroll
-  for (int i = 0; i < KPT; ++i) {
-    if (rk[i] != ~0u) {
-      const uint32_t slot = bins[rk[i] & (kHvBins - 1)] + (rk[i] >> 9);
-      const uint64_t len = o1[i] - o0[i];
-      // a key of 64 KiB or more, or one starting 4 GiB or more past the run's
-      // first key, keeps its index in the run instead of its start (and is
-      // hashed from global memory)
-      const bool near = len < 0xffffu && o0[i] - base16 < 0xffffffffull;
-      s_rel[slot] = near ? (uint32_t)(o0[i] - base16) : tid + i * kHvBlock;
-      s_len[slot] = near ? (uint16_t)len : (uint16_t)0xffffu;
-    }
-  }
-  __syncthreads();
-  STAMP(3);  // slots scattered
-
-  // ---- hash, group g = 64 sorted slots
-  const uint32_t groups = (cnt + kWave - 1) / kWave;
-  uint2 *out = hp + (uint64_t)d.chunk_base * a.C + first;
-  // longest groups first (slots are sorted by length): the waves start on the
-  // groups that set the workgroup's end, and the short ones fill in behind.
-  // (A queue handing each free wave the next group measured the same: the
-  // longest group alone sets the end; so did splitting the longest groups
-  // between two waves by seed, which was slower.)
-  for (uint32_t gi = wave; gi < groups; gi += NW) {
-    const uint32_t g = groups - 1 - gi;
-    const uint32_t s = g * kWave + lane;
-    if (s >= cnt) continue;
-    uint32_t len = s_len[s];
-    const uint32_t r = s_rel[s];
-    uint32_t h1, h2;
-#ifdef ADL_BLOOM_STAMPS
-    if (a.exp & 16) {  // diagnostics: no hashing (wrong pairs)
-      out[s] = make_uint2(r, len | 1u);
-      continue;
-    }
-#endif
-    if (len < 0xffffu && (uint64_t)r + len <= sbytes) {
-      hash_lds(stage, r, len, h1, h2);
-    } else {
-      uint64_t k0 = base16 + r;
-      if (len == 0xffffu) {
-        k0 = keys.offs[kb + r];
-        len = (uint32_t)(keys.offs[kb + r + 1] - k0);
-      }
-      hash_bytes(keys.keys + k0, len, kSeed1, kSeed2, h1, h2);
-    }
-    out[s] = make_uint2(h1, h2);
-  }
-  STAMP(4);  // this wave's groups hashed and stored
+  hash_run<S, kHvBlock>(keys, d.key_begin + first, cnt, ReadWholeBlocks{},
+                        HvOut{hp + (uint64_t)d.chunk_base * a.C + first}, STAMP_HOOK(a));
   STAMP_FLUSH(2);
 }
 
@@ -1673,8 +1554,10 @@ int launch_binned_dt(const Plan &p, Keys keys, uint8_t *d_bitmaps, void *ws, hip
       // skipping needs the keys in order: the generic pass A below.)
       if (p.a.k == 6 && p.a.stage_keys && !p.a.dedup) {
         if (int r = adl_host::lds_limit<hash_var_kernel<kHvKeys, DT>>()) return r;
-        hipExtLaunchKernelGGL(hash_var_kernel<kHvKeys, DT>, dim3(p.total_sc), dim3(kHvBlock), hv_lds_bytes<kHvKeys>(),
-                              st, ev ? ev[0] : nullptr, nullptr, 0, aa, keys, hp, p.total_sc, ft);
+        static_assert(run_lds_bytes<512>(false) == 29712, "the run's LDS at the measured shape");
+        hipExtLaunchKernelGGL(hash_var_kernel<kHvKeys, DT>, dim3(p.total_sc), dim3(kHvBlock),
+                              run_lds_bytes<kHvKeys>(false), st, ev ? ev[0] : nullptr, nullptr, 0, aa, keys, hp,
+                              p.total_sc, ft);
         ADL_HIP_TRY(hipGetLastError());
         // the repeated-hash table pays for 16-byte keys only (configs[2]'s keys
         // repeat few pairs: pass B 64 -> 70 us with it)

@@ -49,6 +49,7 @@ struct Keys16 {
 struct KeysStride {
   const uint8_t *keys;
   uint32_t stride;
+  __device__ __forceinline__ uint64_t off(uint64_t i) const { return i * stride; }  // key i's first byte
   __device__ __forceinline__ void hash(uint64_t i, uint32_t &h1, uint32_t &h2) const {
     hash_bytes(keys + i * stride, stride, kSeed1, kSeed2, h1, h2);
   }
@@ -64,6 +65,7 @@ struct KeysStride {
 struct KeysVar {
   const uint8_t *keys;
   const uint64_t *offs;
+  __device__ __forceinline__ uint64_t off(uint64_t i) const { return offs[i]; }
   __device__ __forceinline__ void hash(uint64_t i, uint32_t &h1, uint32_t &h2) const {
     const uint64_t o0 = offs[i], o1 = offs[i + 1];
     hash_bytes(keys + o0, (uint32_t)(o1 - o0), kSeed1, kSeed2, h1, h2);

@@ -47,6 +47,7 @@
 #include <algorithm>
 
 #include "bloom_common.hpp"
+#include "hash_run.hpp"
 
 using namespace adl_dev;
 
@@ -362,177 +363,25 @@ __device__ __forceinline__ void load_runs(const uint32_t *cnt, const uint32_t *s
 // Both hashes of every query whose keys are not aligned 16-byte keys
 // (variable length, or a fixed stride other than 16, at any alignment), to
 // qh[i] at the query's own index i; K3 then takes the pairs instead of keys.
-// One workgroup per run of S consecutive queries:
-//   load   the run's offsets and its key bytes -- whole 16-byte blocks of
-//          memory from the block holding the run's first byte, up to kStage
-//          bytes -- all requested before the first is used (clamped indices);
-//   sort   the keys counted into kPhBins exact-length bins in LDS, each key's
-//          (start, length, index in the run) scattered to its sorted slot, so
-//          that the 64 keys a wave hashes in lockstep are about equally long;
-//   hash   wave w takes groups of 64 sorted slots, longest first, each lane one
-//          key from LDS (hash_lds); a key past the staged bytes, one of 64 KiB
-//          or more, or one 4 GiB or more past the run's first block is hashed
-//          from global memory (hash_bytes);
-//   out    qh[first query of the run + index in the run] = (h1, h2).
-// (The run staging is like the build's hash_var_kernel, bloom_build.hip, whose
-// output order and alignment contract differ; the likeness is accepted.)
-//
-// Read contract (include/adl_bloom.h: any alignment, no byte outside a key is
-// read): the batch's keys are the byte range [keys + off(0), keys + off(n)).
-// A staged 16-byte block that lies inside that range holds only bytes of this
-// batch's keys and is loaded whole.  The block the range starts in and the one
-// it ends in may reach outside it: of those two only the bytes inside the
-// range are loaded, one at a time (`edge` below).  A run of empty keys loads
-// nothing.  hash_bytes reads a key's own bytes only.
+// One workgroup per run of S consecutive queries, hashed from LDS in length
+// order (hash_run.hpp); the grid is ceil(n / S).  No byte outside the batch's
+// keys is read (ReadExactBytes; include/adl_bloom.h).
 constexpr int kPhBlk = 256;
-constexpr uint32_t kPhRun = 512;   // queries per run (the build's measured shape)
-constexpr uint32_t kPhBins = 512;  // exact key length 0..510; 511 = longer
+constexpr uint32_t kPhRun = 512;  // queries per run (the build's measured shape)
 
-struct QVar {  // key i = keys[offs[i] .. offs[i+1])
-  const uint8_t *keys;
-  const uint64_t *offs;
-  __device__ __forceinline__ uint64_t off(uint64_t i) const { return offs[i]; }
+struct PhOut {  // at the query's own index
+  uint2 *qh;
+  static constexpr bool kByIndex = true;
+  __device__ __forceinline__ void operator()(uint32_t, uint32_t ix, uint32_t h1, uint32_t h2) const {
+    qh[ix] = make_uint2(h1, h2);
+  }
 };
-
-struct QStride {  // key i = keys[i * stride .. (i+1) * stride)
-  const uint8_t *keys;
-  uint32_t stride;
-  __device__ __forceinline__ uint64_t off(uint64_t i) const { return i * stride; }
-};
-
-template <uint32_t S>
-constexpr uint32_t ph_stage_bytes() {
-  return S * 48;  // LDS staging of a run's key bytes (mean var-len key ~40 B)
-}
-
-template <uint32_t S>
-constexpr size_t ph_lds_bytes() {
-  return kPhBins * 4 + S * 4 + S * 2 + S * 2 + ph_stage_bytes<S>() + 16;  // + hash_lds's read slack
-}
 
 template <uint32_t S, class Keys>
 __global__ __launch_bounds__(kPhBlk) void pb_hash_kernel(Keys keys, uint64_t n, uint2 *__restrict__ qh) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  uint32_t *bins = lds;                                        // kPhBins
-  uint32_t *s_rel = lds + kPhBins;                             // key start - base16, by sorted slot
-  uint16_t *s_len = reinterpret_cast<uint16_t *>(s_rel + S);   // length (0xffff: hashed from global memory)
-  uint16_t *s_idx = s_len + S;                                 // index in the run
-  uint32_t *stage = reinterpret_cast<uint32_t *>(s_idx + S);   // 16-byte aligned (S % 4 == 0)
-  static_assert(S % kPhBlk == 0 && S <= 512, "whole rounds of keys per thread; the rank fits 9 bits");
-  constexpr int KPT = S / kPhBlk;
-  constexpr uint32_t NW = kPhBlk / kWave;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const uint64_t q0 = (uint64_t)blockIdx.x * S;  // (the grid is ceil(n / S): q0 < n)
+  const uint64_t q0 = (uint64_t)blockIdx.x * S;
   const uint32_t cnt = (uint32_t)min((uint64_t)S, n - q0);
-  const uint64_t kaddr = reinterpret_cast<uintptr_t>(keys.keys);
-  // addresses: the batch's byte range, the run's, and the run's first block
-  const uint64_t lo = kaddr + keys.off(0), hi = kaddr + keys.off(n);
-  const uint64_t rb = kaddr + keys.off(q0), re = kaddr + keys.off(q0 + cnt);
-  const uint64_t base16 = rb & ~15ull;
-  constexpr uint32_t kStage = ph_stage_bytes<S>();
-  static_assert(kStage % (16 * kPhBlk) == 0, "the staging loads cover kStage in whole rounds of 16 B per thread");
-  // staged: bytes [base16, base16 + 16 * nv), each block holding a byte of the run
-  const uint32_t nv = re > rb ? (uint32_t)(min((re - base16 + 15) & ~15ull, (uint64_t)kStage) / 16) : 0u;
-  const uint32_t sbytes = nv * 16;
-  // blocks [vb, ve) lie inside the batch's range; block 0 and block nv - 1 may not
-  const uint32_t vb = base16 < lo ? 1u : 0u;
-  const uint32_t ve = (nv && base16 + 16ull * nv > hi) ? nv - 1u : nv;
-
-  constexpr int VPT = kStage / 16 / kPhBlk;
-  for (uint32_t i = tid; i < kPhBins; i += kPhBlk) bins[i] = 0;
-  uint64_t o0[KPT], o1[KPT];
-#pragma unroll
-  for (int i = 0; i < KPT; ++i) {
-    const uint32_t idx = min((uint32_t)(tid + i * kPhBlk), cnt - 1u);
-    o0[i] = keys.off(q0 + idx);
-    o1[i] = keys.off(q0 + idx + 1);
-  }
-  u32x4_t v[VPT];  // (the ext-vector type: an array of uint4 held across the barrier goes to scratch)
-  if (vb < ve) {
-    const u32x4_t *src = reinterpret_cast<const u32x4_t *>(base16);
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) v[i] = src[min(max((uint32_t)(tid + i * kPhBlk), vb), ve - 1u)];
-  }
-  // edge: threads 0..15 take the bytes of block 0, threads 16..31 those of
-  // block nv - 1, where that block is not loaded whole; only bytes inside the
-  // batch's range
-  uint32_t edge_at = ~0u, edge_byte = 0;
-  if (tid < 32 && nv) {
-    const uint32_t blk = tid < 16 ? 0u : nv - 1u;
-    const bool partial = tid < 16 ? vb != 0u : (ve < nv && !(nv == 1u && vb != 0u));
-    const uint64_t a = base16 + 16ull * blk + (tid & 15);
-    if (partial && a >= lo && a < hi) {
-      edge_at = 16u * blk + (tid & 15);
-      edge_byte = *reinterpret_cast<const uint8_t *>(a);
-    }
-  }
-  __syncthreads();
-  // ---- sort the run's keys by length
-  uint32_t rk[KPT];
-#pragma unroll
-  for (int i = 0; i < KPT; ++i) {
-    rk[i] = ~0u;
-    if (tid + i * kPhBlk < cnt) {
-      const uint32_t c = (uint32_t)min(o1[i] - o0[i], (uint64_t)(kPhBins - 1));
-      rk[i] = (atomicAdd(&bins[c], 1u) << 9) | c;
-    }
-  }
-  {
-    u32x4_t *dst = reinterpret_cast<u32x4_t *>(stage);
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-      const uint32_t j = tid + i * kPhBlk;
-      if (j >= vb && j < ve) dst[j] = v[i];
-    }
-    if (edge_at != ~0u) reinterpret_cast<uint8_t *>(stage)[edge_at] = (uint8_t)edge_byte;
-  }
-  __syncthreads();
-  if (wave == 0) {  // exclusive scan of the bins, 8 per lane
-    constexpr int PER = kPhBins / kWave;
-    uint32_t bv[PER], t = 0;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) bv[j] = bins[lane * PER + j], t += bv[j];
-    uint32_t run = wave_incl_scan(t, lane) - t;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) bins[lane * PER + j] = run, run += bv[j];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < KPT; ++i) {
-    if (rk[i] != ~0u) {
-      const uint32_t slot = bins[rk[i] & (kPhBins - 1)] + (rk[i] >> 9);
-      const uint64_t len = o1[i] - o0[i], rel = kaddr + o0[i] - base16;
-      // a key of 64 KiB or more, or one starting 4 GiB or more past the run's
-      // first block, is found again by its index (and hashed from global memory)
-      const bool near = len < 0xffffu && rel < 0xffffffffull;
-      s_rel[slot] = near ? (uint32_t)rel : 0u;
-      s_len[slot] = near ? (uint16_t)len : (uint16_t)0xffffu;
-      s_idx[slot] = (uint16_t)(tid + i * kPhBlk);
-    }
-  }
-  __syncthreads();
-  // ---- hash, group g = 64 sorted slots; longest groups first (slots are
-  // sorted by length): the waves start on the groups that set the workgroup's end
-  const uint32_t groups = (cnt + kWave - 1) / kWave;
-  for (uint32_t gi = wave; gi < groups; gi += NW) {
-    const uint32_t s = (groups - 1 - gi) * kWave + lane;
-    if (s >= cnt) continue;
-    uint32_t len = s_len[s];
-    const uint32_t r = s_rel[s], ix = s_idx[s];
-    uint32_t h1, h2;
-    if (len < 0xffffu && (uint64_t)r + len <= sbytes) {
-      hash_lds(stage, r, len, h1, h2);
-    } else {
-      const uint8_t *p = reinterpret_cast<const uint8_t *>(base16 + r);
-      if (len == 0xffffu) {
-        const uint64_t k0 = keys.off(q0 + ix);
-        len = (uint32_t)(keys.off(q0 + ix + 1) - k0);
-        p = keys.keys + k0;
-      }
-      hash_bytes(p, len, kSeed1, kSeed2, h1, h2);
-    }
-    qh[q0 + ix] = make_uint2(h1, h2);
-  }
+  hash_run<S, kPhBlk>(keys, q0, cnt, ReadExactBytes{n}, PhOut{qh + q0});
 }
 
 // ---------------------------------------------------------------- K3
@@ -1238,12 +1087,14 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
       ADL_HIP_TRY(hipGetLastError());
     } else {
       const dim3 runs((uint32_t)((n + kPhRun - 1) / kPhRun));
+      constexpr size_t kLds = run_lds_bytes<kPhRun>(true);
+      static_assert(kLds == 30736, "the run's LDS at the measured shape, with the index array");
       if (shape == Shape::kVar)
-        hipLaunchKernelGGL((pb_hash_kernel<kPhRun, QVar>), runs, dim3(kPhBlk), ph_lds_bytes<kPhRun>(), st,
-                           QVar{d_keys, d_offsets}, n, qh);
+        hipLaunchKernelGGL((pb_hash_kernel<kPhRun, KeysVar>), runs, dim3(kPhBlk), kLds, st,
+                           KeysVar{d_keys, d_offsets}, n, qh);
       else
-        hipLaunchKernelGGL((pb_hash_kernel<kPhRun, QStride>), runs, dim3(kPhBlk), ph_lds_bytes<kPhRun>(), st,
-                           QStride{d_keys, key_stride}, n, qh);
+        hipLaunchKernelGGL((pb_hash_kernel<kPhRun, KeysStride>), runs, dim3(kPhBlk), kLds, st,
+                           KeysStride{d_keys, key_stride}, n, qh);
       ADL_HIP_TRY(hipGetLastError());
       if (int rc = adl_host::lds_limit<pb_scatter_kernel<SrcPairs>>()) return rc;
       hipLaunchKernelGGL(pb_scatter_kernel<SrcPairs>, dim3(p.nb), dim3(kBlk), lds_k3, st, SrcPairs{qh}, d_filter_id, n,
