@@ -59,7 +59,13 @@ EXPORTS = (
     "adl_bloom_probe_fanout_hits_workspace_bytes", "adl_bloom_probe_fanout_hits_device",
     "adl_bloom_revision_multiget",
     "adl_bloom_hits_by_table_workspace_bytes", "adl_bloom_hits_by_table_device", "adl_bloom_revision_read_plan",
+    "adl_bloom_filter_cache_probe_key", "adl_bloom_revision_candidates_host", "adl_bloom_revision_get",
 )
+
+# one resident-server request holds a single-key Get of up to this many tables and key bytes
+# (include/adl_bloom.h: ADL_BLOOM_GET_MAX_TABLES, ADL_BLOOM_GET_MAX_KEY_BYTES)
+GET_MAX_TABLES = 24
+GET_MAX_KEY_BYTES = 96
 
 # entries per workgroup of the grouping kernels (csrc/read_plan.hip, kTile): a tile of the radix sort
 HITS_TILE = 2048
@@ -147,6 +153,12 @@ def lib() -> ctypes.CDLL:
         "adl_bloom_revision_read_plan": (ctypes.c_int, [vp, vp, u32, vp, vp, u64, u32, ctypes.c_int64, vp, vp, u64,
                                                          ctypes.POINTER(u64), vp, u64, ctypes.POINTER(u64), u64,
                                                          ctypes.POINTER(u64), ctypes.POINTER(u64), vp]),
+        "adl_bloom_filter_cache_probe_key": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_char_p), vp, u32, u32, vp, u64,
+                                                             vp, ctypes.POINTER(u64), vp]),
+        "adl_bloom_revision_candidates_host": (ctypes.c_int, [vp, vp, u64, ctypes.c_int64, vp, u32,
+                                                               ctypes.POINTER(u32)]),
+        "adl_bloom_revision_get": (ctypes.c_int, [vp, vp, u32, vp, u64, ctypes.c_int64, vp, u32, ctypes.POINTER(u32),
+                                                   ctypes.POINTER(u32), ctypes.POINTER(u32), vp]),
         "adl_bloom_probe_device": (ctypes.c_int, [vp, vp, u64, u32, i32, vp, u64, vp, vp]),
         "adl_bloom_probe_batch_workspace_bytes": (u64, [u64, u32, i32, u32]),
         "adl_bloom_probe_batch_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, i32, vp, vp, u64, vp]),
@@ -772,6 +784,22 @@ class FilterCache:
                "adl_bloom_filter_cache_probe_fanout")
         return out[:len(tab)], unc.value
 
+    def probe_key(self, oids, key: bytes, filter: int = 0, stream=None):
+        """ONE key against filter `filter` of every table in oids (adl_bloom_filter_cache_probe_key): (0/1 per
+        table, uncached count) -- probe_fanout for one key with all the tables as its list.  Up to GET_MAX_TABLES
+        tables and GET_MAX_KEY_BYTES key bytes are one request to the resident server, with no launch."""
+        key = bytes(key)
+        kb = np.frombuffer(key, dtype=np.uint8) if key else np.zeros(1, np.uint8)
+        arr = (ctypes.c_char_p * max(len(oids), 1))(*oids)
+        lens = np.array([len(o) for o in oids] or [0], dtype=np.uint64)
+        out = np.empty(max(len(oids), 1), dtype=np.uint8)
+        unc = ctypes.c_uint64()
+        _check(lib().adl_bloom_filter_cache_probe_key(self._h, arr, lens.ctypes.data, len(oids), filter,
+                                                      kb.ctypes.data, len(key), out.ctypes.data, ctypes.byref(unc),
+                                                      _host_stream(stream)),
+               "adl_bloom_filter_cache_probe_key")
+        return out[:len(oids)], unc.value
+
     # ---- write-through: a table's filter block built straight into the arena
     class Ticket:
         """A built, unpublished block (adl_bloom_cache_ticket): publish or abandon it.
@@ -1024,6 +1052,42 @@ class Revision:
         rc, hb, ht, _, _, unc = self.multiget_status(cache, keys, offsets, seq, filter, None, 0, stream)
         _check(rc, "adl_bloom_revision_multiget")
         return hb, ht, unc
+
+    def candidates_host(self, key: bytes, seq: int = 2**63 - 1, capacity: int | None = None):
+        """One key's candidate tables over all levels from the levels' host indices, no GPU
+        (adl_bloom_revision_candidates_host): (global ids uint32 in visiting order, their total).  capacity:
+        default the longest list; entries beyond it are not reported."""
+        key = bytes(key)
+        kb = np.frombuffer(key, dtype=np.uint8) if key else np.zeros(1, np.uint8)
+        cap = self.stats()[2] if capacity is None else int(capacity)
+        tab = np.full(max(cap, 1), 0xA5A5A5A5, dtype=np.uint32)
+        num = ctypes.c_uint32()
+        _check(lib().adl_bloom_revision_candidates_host(self._h, kb.ctypes.data, len(key), seq, tab.ctypes.data, cap,
+                                                        ctypes.byref(num)), "adl_bloom_revision_candidates_host")
+        return tab[:min(num.value, cap)], num.value
+
+    def get_status(self, cache: "FilterCache", key: bytes, seq: int = 2**63 - 1, filter: int = 0,
+                   hit_capacity: int | None = None, stream=None):
+        """adl_bloom_revision_get: (status, hit_table, num_hits, num_candidates, uncached).  hit_capacity:
+        default the longest list.  The array starts as 0xA5 bytes; without status 0 nothing is written to it."""
+        key = bytes(key)
+        kb = np.frombuffer(key, dtype=np.uint8) if key else np.zeros(1, np.uint8)
+        cap = self.stats()[2] if hit_capacity is None else int(hit_capacity)
+        ht = np.full(max(cap, 1), 0xA5A5A5A5, dtype=np.uint32)
+        nh, nc, unc = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        rc = lib().adl_bloom_revision_get(self._h, cache._h, filter, kb.ctypes.data, len(key), seq, ht.ctypes.data,
+                                          cap, ctypes.byref(nh), ctypes.byref(nc), ctypes.byref(unc),
+                                          _host_stream(stream))
+        return rc, ht[:min(nh.value, cap)] if rc == ADL_OK else ht[:cap], nh.value, nc.value, unc.value
+
+    def get(self, cache: "FilterCache", key: bytes, seq: int = 2**63 - 1, filter: int = 0, stream=None):
+        """Revision Get of one key -- DB::Get's filter stage: (hit_table, uncached), the tables still to read as
+        global ids in visiting order; multiget's list for that key.  The candidates are selected on the host and
+        asked about in ONE request to the cache's resident server (no launch) when they are at most
+        GET_MAX_TABLES and the key at most GET_MAX_KEY_BYTES bytes; otherwise one launched fan-out probe."""
+        rc, ht, _, _, unc = self.get_status(cache, key, seq, filter, None, stream)
+        _check(rc, "adl_bloom_revision_get")
+        return ht, unc
 
     def read_plan_status(self, cache: "FilterCache", keys: np.ndarray, offsets=None, seq: int = 2**63 - 1,
                          filter: int = 0, entry_capacity: int | None = None, group_capacity: int | None = None,

@@ -221,17 +221,16 @@ bool watch_answers(const volatile uint8_t *ans, uint64_t n, hipEvent_t done, int
   }
 }
 
-// A single-key Get (up to adl_srv::kMaxQ queries) asks the cache's resident
-// server: no launch.  Its answers arrive, in h_out, after all its reads of the
-// pinned ranges.  adl_srv::kBusy: not served -- the batch is not eligible, the
-// server is switched off, missing or backing off, or no answer came in
-// adl_srv::kTimeout (a healthy GPU with no room for the server's wave) -- and
-// the caller probes by a launch, the ranges still pinned.
-int serve_resident(adl_bloom_filter_cache *c, const Resolved &res, uint32_t num_tables, const uint8_t *h_keys,
-                   const uint64_t *h_offsets, uint64_t n, uint32_t key_stride, const uint32_t *h_table,
-                   uint8_t *h_out) {
-  const uint64_t kbytes = h_offsets ? h_offsets[n] - h_offsets[0] : n * (uint64_t)key_stride;
-  if (!adl_srv::eligible(n, kbytes) || !adl_host::knobs().probe_server) return adl_srv::kBusy;
+// A single-key Get asks the cache's resident server: no launch.  Its answers
+// arrive, in h_out, after all its reads of the pinned ranges.  ask(server,
+// arena epoch) posts the request (adl_srv::probe or adl_srv::probe_fan).
+// adl_srv::kBusy: not served -- the request is not eligible, the server is
+// switched off, missing or backing off, or no answer came in adl_srv::kTimeout
+// (a healthy GPU with no room for the server's wave) -- and the caller probes
+// by a launch, the ranges still pinned.
+template <class Ask>
+int ask_server(adl_bloom_filter_cache *c, bool eligible, Ask &&ask) {
+  if (!eligible || !adl_host::knobs().probe_server) return adl_srv::kBusy;
   const int64_t now_ns =
       std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
   if (now_ns < c->srv_backoff_until.load(std::memory_order_relaxed)) return adl_srv::kBusy;
@@ -245,19 +244,44 @@ int serve_resident(adl_bloom_filter_cache *c, const Resolved &res, uint32_t num_
     srv = c->srv;
   }
   if (!srv) return adl_srv::kBusy;
-  uint64_t rng[2 * adl_srv::kMaxQ];
-  uint8_t kq[adl_srv::kMaxQ];
-  const uint64_t a0 = reinterpret_cast<uint64_t>(c->arena);
-  for (uint64_t i = 0; i < n; ++i) {
-    rng[2 * i] = a0 + res.be[h_table[i]];
-    rng[2 * i + 1] = a0 + res.be[num_tables + h_table[i]];
-    kq[i] = res.kt[h_table[i]];
-  }
-  int rc = adl_srv::probe(srv, h_keys, h_offsets, key_stride, n, rng, kq, c->epoch.load(std::memory_order_acquire),
-                          h_out);
+  int rc = ask(srv, c->epoch.load(std::memory_order_acquire));
   if (rc == ADL_OK && adl_host::g_test_faults.take(ADL_TEST_FAULT_CACHE_COMPLETION) >= 0) rc = ADL_ERR_DEVICE;
   if (rc == adl_srv::kBusy) c->srv_backoff_until.store(now_ns + kServerBackoffNs, std::memory_order_relaxed);
   return rc;
+}
+
+// Up to adl_srv::kMaxQ queries, each with its own key, in one server request.
+int serve_resident(adl_bloom_filter_cache *c, const Resolved &res, uint32_t num_tables, const uint8_t *h_keys,
+                   const uint64_t *h_offsets, uint64_t n, uint32_t key_stride, const uint32_t *h_table,
+                   uint8_t *h_out) {
+  const uint64_t kbytes = h_offsets ? h_offsets[n] - h_offsets[0] : n * (uint64_t)key_stride;
+  return ask_server(c, adl_srv::eligible(n, kbytes), [&](adl_srv::Server *srv, uint64_t epoch) {
+    uint64_t rng[2 * adl_srv::kMaxQ];
+    uint8_t kq[adl_srv::kMaxQ];
+    const uint64_t a0 = reinterpret_cast<uint64_t>(c->arena);
+    for (uint64_t i = 0; i < n; ++i) {
+      rng[2 * i] = a0 + res.be[h_table[i]];
+      rng[2 * i + 1] = a0 + res.be[num_tables + h_table[i]];
+      kq[i] = res.kt[h_table[i]];
+    }
+    return adl_srv::probe(srv, h_keys, h_offsets, key_stride, n, rng, kq, epoch, h_out);
+  });
+}
+
+// ONE key against every resolved table (0 .. num_tables-1), in one server
+// request of the fan form: up to adl_srv::kFanTables tables, a key of up to
+// adl_srv::kFanKeyBytes bytes.
+int serve_resident_key(adl_bloom_filter_cache *c, const Resolved &res, uint32_t num_tables, const uint8_t *h_key,
+                       uint64_t key_len, uint8_t *h_out) {
+  return ask_server(c, adl_srv::eligible_fan(num_tables, key_len), [&](adl_srv::Server *srv, uint64_t epoch) {
+    uint64_t rng[2 * adl_srv::kFanTables];
+    const uint64_t a0 = reinterpret_cast<uint64_t>(c->arena);
+    for (uint32_t t = 0; t < num_tables; ++t) {
+      rng[2 * t] = a0 + res.be[t];
+      rng[2 * t + 1] = a0 + res.be[num_tables + t];
+    }
+    return adl_srv::probe_fan(srv, h_key, key_len, num_tables, rng, res.kt.data(), epoch, h_out);
+  });
 }
 
 // The body of a batch that answers a byte per query: the plan's sections up
@@ -329,6 +353,55 @@ int fetch_count_first(adl_host::Staging &sg, uint64_t o_counts, uint64_t o_paylo
   });
   if (second && hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
   return rc;
+}
+
+// The launched fan-out probe of resolved tables: keys (once each), their
+// offsets, the begin array, the table ids and the range and k tables up, one
+// fan-out launch, a byte per pair down.
+int launch_fanout(adl_bloom_filter_cache *c, const Resolved &res, uint32_t num_tables, const uint8_t *h_keys,
+                  const uint64_t *h_offsets, uint64_t num_keys, uint32_t key_stride, const uint32_t *h_pair_begin,
+                  const uint32_t *h_pair_table, uint64_t np, uint8_t *h_out, hipStream_t st) {
+  adl_host::StagePlan plan;
+  const adl_host::KeyBlock kb(plan, h_offsets, num_keys, key_stride);
+  const uint64_t o_pb = plan.take((num_keys + 1) * 4);
+  const uint64_t o_pt = plan.take(np * 4);
+  const TableBlock tb(plan, res);
+  const uint64_t o_out = plan.take(np);
+  return run_answer_batch(
+      plan, o_out, np, st,
+      [&](uint8_t *hbuf) {
+        kb.fill(hbuf, h_keys, h_offsets);
+        memcpy(hbuf + o_pb, h_pair_begin, (num_keys + 1) * 4);
+        memcpy(hbuf + o_pt, h_pair_table, np * 4);
+        tb.fill(hbuf, res);
+      },
+      [&](uint8_t *dbuf, hipEvent_t done) {
+        return adl_host::adl_probe_fanout_device_ev(
+            dbuf, kb.offsets(dbuf), num_keys, key_stride, reinterpret_cast<const uint32_t *>(dbuf + o_pb),
+            reinterpret_cast<const uint32_t *>(dbuf + o_pt), np, num_tables, c->arena, tb.begin(dbuf),
+            tb.begin(dbuf) + num_tables, tb.k(dbuf), dbuf + o_out, st, done);
+      },
+      h_out);
+}
+
+// 0, 1, 2, ...: the candidate list of a one-key fan-out over every listed
+// table (per-thread, grown once).
+thread_local std::vector<uint32_t> t_iota;
+
+// One key against every resolved table (0 .. num_tables-1, >= 1), h_out[t] its
+// answer: one request of the fan form to the resident server, or -- more
+// tables or a longer key than that takes, or the server not serving -- the
+// launched fan-out probe of one key with all the tables as its list.
+int probe_key_resolved(adl_bloom_filter_cache *c, const Resolved &res, uint32_t num_tables, const uint8_t *h_key,
+                       uint64_t key_len, uint8_t *h_out, hipStream_t st) {
+  int rc = serve_resident_key(c, res, num_tables, h_key, key_len, h_out);
+  if (rc != adl_srv::kBusy) return rc;
+  while (t_iota.size() < num_tables) t_iota.push_back((uint32_t)t_iota.size());
+  static const uint8_t no_bytes[1] = {0};  // (an empty key still has an address)
+  const uint64_t off[2] = {0, key_len};
+  const uint32_t pb[2] = {0, num_tables};
+  return launch_fanout(c, res, num_tables, h_key ? h_key : no_bytes, off, 1, 0, pb, t_iota.data(), num_tables, h_out,
+                       st);
 }
 
 }  // namespace
@@ -554,31 +627,34 @@ int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *c, const char *c
     resolve_tables(c, oids, oid_lens, num_tables, filter, res);
     uint64_t uncached = 0;
     for (uint64_t p = 0; p < np; ++p) uncached += !res.cached[h_pair_table[p]];
-    // 2. without the lock: keys (once each), their offsets, the begin array,
-    //    the table ids and the range and k tables up, one fan-out launch, a
-    //    byte per pair down
-    adl_host::StagePlan plan;
-    const adl_host::KeyBlock kb(plan, h_offsets, num_keys, key_stride);
-    const uint64_t o_pb = plan.take((num_keys + 1) * 4);
-    const uint64_t o_pt = plan.take(np * 4);
-    const TableBlock tb(plan, res);
-    const uint64_t o_out = plan.take(np);
-    const int rc = run_answer_batch(
-        plan, o_out, np, st,
-        [&](uint8_t *hbuf) {
-          kb.fill(hbuf, h_keys, h_offsets);
-          memcpy(hbuf + o_pb, h_pair_begin, (num_keys + 1) * 4);
-          memcpy(hbuf + o_pt, h_pair_table, np * 4);
-          tb.fill(hbuf, res);
-        },
-        [&](uint8_t *dbuf, hipEvent_t done) {
-          return adl_host::adl_probe_fanout_device_ev(
-              dbuf, kb.offsets(dbuf), num_keys, key_stride, reinterpret_cast<const uint32_t *>(dbuf + o_pb),
-              reinterpret_cast<const uint32_t *>(dbuf + o_pt), np, num_tables, c->arena, tb.begin(dbuf),
-              tb.begin(dbuf) + num_tables, tb.k(dbuf), dbuf + o_out, st, done);
-        },
-        h_out);
+    // 2. without the lock: one fan-out launch
+    const int rc = launch_fanout(c, res, num_tables, h_keys, h_offsets, num_keys, key_stride, h_pair_begin,
+                                 h_pair_table, np, h_out, st);
     if (rc) return rc;
+    if (h_uncached) *h_uncached = uncached;
+    return ADL_OK;
+  } catch (...) {
+    return ADL_ERR_OUT_OF_MEMORY;
+  }
+}
+
+int adl_bloom_filter_cache_probe_key(adl_bloom_filter_cache *c, const char *const *oids, const uint64_t *oid_lens,
+                                     uint32_t num_tables, uint32_t filter, const uint8_t *h_key, uint64_t key_len,
+                                     uint8_t *h_out, uint64_t *h_uncached, void *stream) {
+  if (!c || (num_tables && (!oids || !oid_lens))) return ADL_ERR_INVALID_ARG;
+  if (h_uncached) *h_uncached = 0;
+  if (num_tables == 0) return ADL_OK;
+  if (!h_out || (key_len && !h_key)) return ADL_ERR_INVALID_ARG;
+  try {
+    hipStream_t st = adl_host::sync_stream(stream);
+    // under the lock: the listed tables' ranges and k, pinned and marked used,
+    // until this call is done with them
+    Resolved &res = t_res;
+    PinScope pins(c, res);
+    resolve_tables(c, oids, oid_lens, num_tables, filter, res);
+    if (int rc = probe_key_resolved(c, res, num_tables, h_key, key_len, h_out, st)) return rc;
+    uint64_t uncached = 0;
+    for (uint32_t t = 0; t < num_tables; ++t) uncached += !res.cached[t];
     if (h_uncached) *h_uncached = uncached;
     return ADL_OK;
   } catch (...) {
@@ -756,6 +832,73 @@ int adl_bloom_revision_multiget(adl_bloom_revision *rev, adl_bloom_filter_cache 
     memcpy(h_hit_begin, hbuf + o_hb, (num_keys + 1) * 4);
     if (nh > hit_capacity) return ADL_ERR_WORKSPACE;
     if (nh) memcpy(h_hit_table, ht, nh * 4);
+    if (h_uncached) *h_uncached = uncached;
+    return ADL_OK;
+  } catch (...) {
+    return ADL_ERR_OUT_OF_MEMORY;
+  }
+}
+
+// The revision multi-get for ONE key -- DB::Get's filter stage.  The key's
+// candidate tables are selected in the levels' host indices (no device copy of
+// the revision is made or used), ONLY their oids are resolved and pinned (a
+// Get does not walk the revision's whole oid list under the cache's mutex),
+// one request of the fan form asks the resident server about all of them, and
+// the survivors are compacted here.  Per-thread scratch: nothing is allocated
+// per call once it has grown.
+int adl_bloom_revision_get(adl_bloom_revision *rev, adl_bloom_filter_cache *c, uint32_t filter, const uint8_t *h_key,
+                           uint64_t key_len, int64_t seq, uint32_t *h_hit_table, uint32_t hit_capacity,
+                           uint32_t *num_hits, uint32_t *num_candidates, uint32_t *h_uncached, void *stream) {
+  if (!rev || !c || !num_hits || (key_len && !h_key) || (hit_capacity && !h_hit_table)) return ADL_ERR_INVALID_ARG;
+  *num_hits = 0;
+  if (num_candidates) *num_candidates = 0;
+  if (h_uncached) *h_uncached = 0;
+  for (adl_bloom_level *lv : rev->levels)
+    if (lv && lv->ix.num_tables && lv->oids.size() != lv->ix.num_tables) return ADL_ERR_INVALID_ARG;  // no oids
+  try {
+    struct Scratch {
+      std::vector<uint32_t> cand;
+      std::vector<const char *> op;
+      std::vector<uint64_t> ol;
+      std::vector<uint8_t> ans;
+    };
+    thread_local Scratch sc;
+    // 1. selection on the host (no key has more candidates than rev->longest)
+    if (sc.cand.size() < rev->longest) sc.cand.resize(rev->longest);
+    uint32_t n = 0;
+    if (int rc = adl_bloom_revision_candidates_host(rev, h_key, key_len, seq, sc.cand.data(), (uint32_t)sc.cand.size(),
+                                                    &n))
+      return rc;
+    if (num_candidates) *num_candidates = n;
+    if (n == 0) return ADL_OK;
+    // 2. the candidates' oids (a global id's level: the last base not above it)
+    sc.op.resize(n);
+    sc.ol.resize(n);
+    sc.ans.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      const size_t l = std::upper_bound(rev->table_base.begin(), rev->table_base.end(), sc.cand[i]) -
+                       rev->table_base.begin() - 1;
+      const std::string &oid = rev->levels[l]->oids[sc.cand[i] - rev->table_base[l]];
+      sc.op[i] = oid.data();
+      sc.ol[i] = oid.size();
+    }
+    hipStream_t st = adl_host::sync_stream(stream);
+    // 3. under the lock: their ranges and k, pinned and marked used; then one request
+    Resolved &res = t_res;
+    PinScope pins(c, res);
+    resolve_tables(c, sc.op.data(), sc.ol.data(), n, filter, res);
+    if (int rc = probe_key_resolved(c, res, n, h_key, key_len, sc.ans.data(), st)) return rc;
+    // 4. the survivors, in visiting order
+    uint32_t nh = 0, uncached = 0;
+    for (uint32_t i = 0; i < n; ++i) nh += sc.ans[i] != 0;
+    *num_hits = nh;
+    if (nh > hit_capacity) return ADL_ERR_WORKSPACE;
+    nh = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (!sc.ans[i]) continue;
+      h_hit_table[nh++] = sc.cand[i];
+      uncached += !res.cached[i];
+    }
     if (h_uncached) *h_uncached = uncached;
     return ADL_OK;
   } catch (...) {

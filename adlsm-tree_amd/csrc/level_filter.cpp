@@ -490,6 +490,33 @@ RC RevisionMultiGetFilter(FilterCache &cache, RevisionIndex &rev, const vector<s
   return OK;
 }
 
+RC RevisionGetFilter(FilterCache &cache, RevisionIndex &rev, string_view user_key, int64_t seq,
+                     RevisionGetResult &out) {
+  out.table.clear();
+  out.level.clear();
+  out.candidates = out.uncached = 0;
+  if (rev.status()) return rev.status();
+  adl_bloom_revision *h = rev.handle();
+  if (!h) return rev.device_status();
+  if (!cache.handle()) return cache.status();
+  const vector<uint32_t> &base = rev.table_base();
+  // no key has more candidates, so no call comes back short of room
+  out.table.resize(rev.longest_list());
+  uint32_t nh = 0;
+  const int st = adl_bloom_revision_get(h, cache.handle(), 0, reinterpret_cast<const uint8_t *>(user_key.data()),
+                                        user_key.size(), seq, out.table.data(), (uint32_t)out.table.size(), &nh,
+                                        &out.candidates, &out.uncached, nullptr);
+  if (st != ADL_OK) {
+    out.table.clear();
+    return FromStatus(st);
+  }
+  out.table.resize(nh);
+  out.level.resize(nh);
+  for (uint32_t p = 0; p < nh; ++p)
+    out.level[p] = (uint8_t)(std::upper_bound(base.begin(), base.end(), out.table[p]) - base.begin() - 1);
+  return OK;
+}
+
 namespace {
 
 /* group_level and level_begin of a plan whose group_table is set */

@@ -203,6 +203,24 @@ struct RevisionMultiGetResult {
 RC RevisionMultiGetFilter(FilterCache &cache, RevisionIndex &rev, const vector<string_view> &user_keys, int64_t seq,
                           RevisionMultiGetResult &out);
 
+struct RevisionGetResult {
+  vector<uint32_t> table;  /* global ids of the tables still to read, in Revision::Get's visiting order */
+  vector<uint8_t> level;   /* the level of each */
+  uint32_t candidates = 0; /* the tables that cover the key, over all levels */
+  uint32_t uncached = 0;   /* hits whose table was not in the cache (answered 1) */
+};
+
+/* The filter stage of Revision::Get for ONE key -- DB::Get: the list
+ * RevisionMultiGetFilter gives for that key.  The candidates are selected in
+ * the levels' host indices, only their oids are resolved in the cache, and all
+ * of them are asked about in one request to the cache's resident probe server
+ * (adl_bloom_revision_get): no launch for up to ADL_BLOOM_GET_MAX_TABLES (24)
+ * candidates and a key of up to ADL_BLOOM_GET_MAX_KEY_BYTES (96) bytes, one
+ * launched fan-out probe beyond.  A caller that keeps `out` across calls
+ * allocates nothing per call. */
+RC RevisionGetFilter(FilterCache &cache, RevisionIndex &rev, string_view user_key, int64_t seq,
+                     RevisionGetResult &out);
+
 /* The hits of a revision multi-get table by table: what a reader that opens
  * each table once works from.  Level::Get reads every candidate table of a
  * level and keeps the smallest inner key (src/revision.cpp:279-308), so within

@@ -228,6 +228,23 @@ inline void Lookup(const Index &ix, size_t K, KeyAt &&key_at, int64_t seq, uint3
   else LookupImpl<false>(ix, K, key_at, seq, begin, table);
 }
 
+/* Lookup for ONE key, with no allocation: emit(t) for each candidate table of
+ * user key u at `seq`, in visiting order; returns their number.  (The
+ * branching search: a single Get is the small, repeated batch.) */
+template <class Emit>
+inline uint32_t LookupOne(const Index &ix, std::string_view u, int64_t seq, Emit &&emit) {
+  if (!ix.num_tables) return 0;
+  const uint32_t r = ix.template region<false>(u);
+  uint32_t n = 0;
+  for (uint32_t p = ix.rbeg[r]; p < ix.rbeg[r + 1]; ++p) {
+    const uint32_t e = ix.rlist[p];
+    if ((r & 1) && ix.gone(e, seq)) continue;  // only a point region lists tables at their own max user key
+    emit(e & kTableMask);
+    ++n;
+  }
+  return n;
+}
+
 /* What Build knows before it builds any list: the tables decoded and in
  * files_meta_ order, who enters and leaves at each boundary, and the size of
  * the lists.  (LevelCandidates stops here when a direct scan is cheaper.) */

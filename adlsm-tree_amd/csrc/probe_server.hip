@@ -32,6 +32,15 @@
 //                    above the 8 answer bits.  Both in one 8-byte system-scope
 //                    store; the host takes its answers from word 1 alone
 //
+// A slot can carry a second form, the fan form: ONE key and up to 24 filter
+// ranges (FanSlot) -- a revision Get, the key asked of every candidate table
+// of every level.  The slot's header names the form (the bell has no bit
+// left); after the group's ordinary queries the whole wave serves each such
+// slot, lane t its table t, the key hashed from the same LDS words by every
+// lane.  Its answers 8-23 go into two more tagged words of the done line
+// (pad[10], pad[11]: one 8-byte store), and the host takes an answer only
+// from words that carry its request's tag.
+//
 // The wave polls the bells and the inline lines, copies pending slots into LDS
 // four at a time (one load per lane per slot, one round trip for the group;
 // an inline request is copied from the lines already in LDS), hashes each query's
@@ -66,7 +75,11 @@
 // answer tag and of kSeqMask (ADL_TEST_FAULT_SERVER_SEQ presets a slot's
 // sequence): tests/test_gpu_probe_server_geometry.py over the case table of
 // tests/serverkeys.py, which tests/test_probe_server_cases_cpu.py holds to the
-// oracle without a GPU.
+// oracle without a GPU.  The fan form -- 1..25 tables, each answer bit of the
+// three tagged words alone, key lengths 0..97, mixed k and filter sizes, the
+// forms in turn on one slot, the wraps, 72 threads:
+// tests/test_gpu_revision_get.py over tests/getkeys.py
+// (tests/test_revision_get_cpu.py).
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -92,7 +105,7 @@ namespace {
 constexpr uint32_t kSlots = 64;      // one per lane of the server wave
 constexpr uint32_t kSlotBytes = 512;
 constexpr uint32_t kGroup = 4;       // slots staged in LDS at a time (2 KiB)
-constexpr uint32_t kHdrBytes = 16;   // seq (unused by the device), n, (unused), key bytes
+constexpr uint32_t kHdrBytes = 16;   // seq (unused by the device), n, the slot's form, key bytes
 constexpr uint32_t kInlineSlots = 4;       // slots whose one-query requests can sit in their bell line
 constexpr uint32_t kInlineKeyBytes = 40;
 constexpr uint32_t kInlineBit = 0x80000000u;  // in a bell: the request is in the slot's line
@@ -118,7 +131,7 @@ constexpr uint32_t kKeyOff = kKoffOff + 2 * (adl_srv::kMaxQ + 8);
 static_assert(kKeyOff % 16 == 0 && kKeyOff + adl_srv::kMaxKeyBytes + 16 <= kSlotBytes, "slot layout");
 
 struct Slot {
-  uint32_t seq, n, unused, key_bytes;
+  uint32_t seq, n, form, key_bytes;  // form: 0 (this layout) or kFormFan (FanSlot)
   uint64_t range[2 * adl_srv::kMaxQ];
   uint16_t koff[adl_srv::kMaxQ + 1];
   uint8_t kq[adl_srv::kMaxQ];  // per query: k
@@ -128,12 +141,35 @@ struct Slot {
 static_assert(offsetof(Slot, keys) == kKeyOff, "slot layout");
 static_assert(sizeof(Slot) == kSlotBytes, "slot size");
 
+// The fan form of a slot: ONE key against n <= kFanTables filter ranges, lane
+// t of the wave testing table t.  The bell's bits are all taken, so the form
+// is known from the staged slot's header alone.
+constexpr uint32_t kFormFan = 1;
+struct FanEntry {
+  uint64_t begin;  // filter range start (device address in the cache arena)
+  uint32_t len;    // filter range bytes (0xFFFFFFFF: more, answers 0 as any range of 2^31 bits or more)
+  uint32_t k;
+};
+constexpr uint32_t kFanKeyOff = kHdrBytes + sizeof(FanEntry) * adl_srv::kFanTables;
+struct FanSlot {
+  uint32_t seq, n, form, key_bytes;
+  FanEntry e[adl_srv::kFanTables];
+  uint8_t key[kSlotBytes - kFanKeyOff];
+};
+static_assert(offsetof(FanSlot, form) == offsetof(Slot, form) && offsetof(FanSlot, key) == kFanKeyOff, "fan layout");
+static_assert(sizeof(FanSlot) == kSlotBytes, "fan slot size");
+// hash_lds reads 8-byte words up to 8 bytes past the key's end
+static_assert(kFanKeyOff % 8 == 0 && kFanKeyOff + adl_srv::kFanKeyBytes + 8 <= kSlotBytes, "fan key within the slot");
+static_assert(adl_srv::kFanTables <= 24, "three tagged words hold 24 answer bits");
+
 struct Done {
   uint32_t seq;
-  uint32_t tagged;  // (seq << 8) | answer bits
-  uint32_t pad[14];
+  uint32_t tagged;  // (seq << 8) | answer bits (a fan request's tables 0-7)
+  uint32_t pad[14];  // [0..9] the phase stamps; [10], [11] a fan request's tables 8-15 and 16-23, tagged alike
 };
 static_assert(sizeof(Done) == 64, "done line");
+constexpr uint32_t kDoneExtra = 10;  // pad[kDoneExtra], pad[kDoneExtra + 1]: one aligned 8-byte store
+static_assert((offsetof(Done, pad) + 4 * kDoneExtra) % 8 == 0, "the extra answer words are one 8-byte store");
 
 // A one-query request inline in its slot's bell line: check = kLineCheck ^ the
 // XOR of line_word_hash(w_i, i) over the other 15 words (the sequence number
@@ -241,6 +277,15 @@ __device__ __forceinline__ Prep prep_slot_query(const Slot &sl, uint32_t q) {
                     kKeyOff + ko, ke - ko);
 }
 
+// Table t of a fan slot staged in LDS: its own range and k, the slot's one
+// key (every lane reads the same LDS words: a broadcast).  Everything read
+// from the slot is clamped, so no LDS read leaves the staged slot.
+__device__ __forceinline__ Prep prep_fan(const FanSlot &fs, uint32_t t) {
+  const FanEntry e = fs.e[t];
+  return prep_query(e.k, e.begin, e.begin + e.len, reinterpret_cast<const uint32_t *>(&fs), kFanKeyOff,
+                    min(fs.key_bytes, adl_srv::kFanKeyBytes));
+}
+
 // The request of line i staged in LDS (lines: the LDS copy of all of them,
 // with slack words after the last).
 __device__ __forceinline__ Prep prep_line(const uint32_t *lines, uint32_t i) {
@@ -257,24 +302,24 @@ __device__ __forceinline__ Prep prep_line(const uint32_t *lines, uint32_t i) {
 // kLdsReserveWords): a Get does not wait for a build.  amdgpu_num_vgpr(16) is
 // doubled for gfx950's unified register file (as kPassARegs' 60 -> 120): the
 // code object's .vgpr_count is 32.  Unconstrained the kernel would take 63, so
-// 13 VGPRs spill to scratch (52 B per lane, with the phase stamps): kernel arguments and loop state,
-// reloaded once per poll and once per served group, from the L1/L2 the wave
-// alone uses.  tools/kernel_resources.py prints both from the built library
+// 13 VGPRs spill to scratch (52 B per lane, with the phase stamps and the fan
+// pass): kernel arguments and loop state, reloaded once per poll and once per
+// served group, from the L1/L2 the wave alone uses.  tools/kernel_resources.py prints both from the built library
 // and tests/test_kernel_resources.py pins them (no other product kernel on the
 // headline, probe or var-len paths spills).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(16))) void probe_server_kernel(
     Area *area, uint64_t idle_ticks, uint64_t life_ticks, uint32_t gen) {
   __shared__ __attribute__((aligned(16))) uint8_t lslot[kGroup][kSlotBytes];
   __shared__ __attribute__((aligned(16))) uint32_t lline[kInlineSlots * 16 + 4];  // the lines of the last poll (+ hash_lds slack)
-  const uint32_t lane = threadIdx.x;
+  const uint32_t lane0 = threadIdx.x;
   // a successor queued behind a running kernel (Server::launcher) announces
   // itself: alive again, and its generation started
-  if (lane == 0) {
+  if (lane0 == 0) {
     __hip_atomic_store(&area->ctl.alive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(&area->ctl.gen_started, gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "");
-  uint32_t served = __hip_atomic_load(&area->done[lane].seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  uint32_t served = __hip_atomic_load(&area->done[lane0].seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   const uint64_t t0 = now_ticks();
   uint64_t last = t0, tprev = t0;
   bool closing = false;
@@ -284,6 +329,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(16))) void probe
   // the compiler spilled the in-flight values and waited for each load before
   // its spill store, serialising the polls again.)
   for (;;) {
+    // (Each poll works the lane's addresses out afresh, from a copy of its
+    // number that the compiler cannot trace: hoisted out of this loop every
+    // one of them -- the lane's bell, its line word, its LDS words, its
+    // query's range and offsets -- takes a register for the kernel's whole
+    // life, and most of those spilled.)
+    uint32_t lane = lane0;
+    asm volatile("" : "+v"(lane));
     const uint64_t tp = now_ticks();  // this poll (diagnostics: the gap since the previous one)
     const uint32_t bell = ld_sys(&area->bell[lane]);
     // the inline lines, in the same round trip: lane l reads word l % 16 of
@@ -354,52 +406,87 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(16))) void probe
 #pragma unroll
       for (uint32_t u = 0; u < kGroup; ++u) reinterpret_cast<uint64_t *>(lslot[u])[lane] = v[u];
       __syncthreads();
-      const uint32_t u = lane / adl_srv::kMaxQ, q = lane % adl_srv::kMaxQ;
-      uint32_t j = kSlots;  // the slot lane 8u + q serves (kSlots: none)
-#pragma unroll
-      for (uint32_t x = 0; x < kGroup; ++x) j = u == x ? js[x] : j;
       const uint64_t t_stage = now_ticks();
-      Prep pr{0ull, 0u, 0u, 0u, 0u};
-      const uint32_t bj = (uint32_t)__shfl((int)bell, (int)(j < kSlots ? j : 0u));
-      if (j < kSlots && (bj & kInlineBit)) {
-        if (q == 0) pr = prep_line(lline, j & (kInlineSlots - 1));
-      } else if (j < kSlots) {
-        const Slot &sl = *reinterpret_cast<const Slot *>(lslot[u]);
-        if (q < min(sl.n, adl_srv::kMaxQ)) pr = prep_slot_query(sl, q);
-      }
-      asm volatile("" ::"v"(pr.h1), "v"(pr.h2));  // the hashes are done before the stamp
-      const uint64_t t_hash = now_ticks();
-      const uint32_t hit = read_bits(pr);
-      asm volatile("" ::"v"(hit));  // the bit reads have returned before the stamp
-      const uint64_t t_reads = now_ticks();
-      const uint64_t hb = __ballot(hit != 0);
-      // lane u < kGroup answers slot js[u]: {seq, (seq << 8) | answer bits} in
-      // one 8-byte system-scope store (a plain store can sit in the device's
-      // write path while the wave keeps polling)
-      uint32_t ju = kSlots;
+      // From a lane's Prep on, both forms of a request run this: the bit
+      // reads, the ballot and the answer.  fp == 0: the group's ordinary
+      // requests, lane 8u + q query q of slot u, lane u < kGroup answers slot
+      // js[u] unless it is in the fan form (fan: bit u); fp == u + 1: the pass
+      // of slot u in the fan form, lane t its table t, lane u answers.
+      auto serve = [&](const Prep &pr, uint32_t fan, uint32_t fp) {
+        asm volatile("" ::"v"(pr.h1), "v"(pr.h2));  // the hashes are done before the stamp
+        const uint64_t t_hash = now_ticks();
+        const uint32_t hit = read_bits(pr);
+        asm volatile("" ::"v"(hit));  // the bit reads have returned before the stamp
+        const uint64_t t_reads = now_ticks();
+        const uint64_t hb = __ballot(hit != 0);
+        // {seq, (seq << 8) | answer bits} in one 8-byte system-scope store (a
+        // plain store can sit in the device's write path while the wave keeps
+        // polling)
+        uint32_t ju = kSlots;
 #pragma unroll
-      for (uint32_t x = 0; x < kGroup; ++x) ju = lane == x ? js[x] : ju;
-      const uint32_t seq = (uint32_t)__shfl((int)bell, (int)(ju < kSlots ? ju : 0u));
-      if (ju < kSlots) {
-        const uint32_t bits = (uint32_t)(hb >> (lane * adl_srv::kMaxQ)) & 0xFFu;
-        const uint64_t word = (uint64_t)seq | ((uint64_t)((seq << 8) | bits) << 32);
-        __hip_atomic_store(reinterpret_cast<uint64_t *>(&area->done[ju]), word, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-        // phase stamps (10-ns ticks from the poll that found the request; the
-        // host folds them into adl_bloom_probe_server_phases at the slot's
-        // next request, and prints them for a slow one under ADL_BLOOM_DEBUG):
-        // {seq, gap since the previous poll}, {poll loads back, slot staged},
-        // {hashed, bits read}, {answer stored, seq}, {the poll's start and the
-        // answer's store on the kernel's clock (low 32 bits), the host
-        // relates them to its own clock to place a slow request's delay}
-        const uint64_t ta = now_ticks();
-        uint64_t *dg = reinterpret_cast<uint64_t *>(&area->done[ju].pad[0]);
-        auto w2 = [](uint64_t a, uint64_t b) { return (uint64_t)(uint32_t)a | ((uint64_t)(uint32_t)b << 32); };
-        __hip_atomic_store(dg + 0, w2(seq, tp - tprev), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(dg + 1, w2(t_polled - tp, t_stage - tp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(dg + 2, w2(t_hash - tp, t_reads - tp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(dg + 4, w2(tp, ta), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(dg + 3, w2(ta - tp, seq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        for (uint32_t x = 0; x < kGroup; ++x)
+          ju = lane == x && (fp ? fp == x + 1 : !((fan >> x) & 1u)) ? js[x] : ju;
+        const uint32_t seq = (uint32_t)__shfl((int)bell, (int)(ju < kSlots ? ju : 0u));
+        if (ju < kSlots) {
+          const uint32_t bits = (uint32_t)(fp ? hb : hb >> (lane * adl_srv::kMaxQ)) & 0xFFu;
+          const uint64_t word = (uint64_t)seq | ((uint64_t)((seq << 8) | bits) << 32);
+          __hip_atomic_store(reinterpret_cast<uint64_t *>(&area->done[ju]), word, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_SYSTEM);
+          if (fp) {
+            // tables 8-15 and 16-23, each word tagged as the first: the host
+            // takes an answer only from words that carry its request's tag, so
+            // the two stores need no order
+            const uint32_t t = seq << 8;
+            const uint64_t extra = (uint64_t)(t | ((uint32_t)(hb >> 8) & 0xFFu)) |
+                                   ((uint64_t)(t | ((uint32_t)(hb >> 16) & 0xFFu)) << 32);
+            __hip_atomic_store(reinterpret_cast<uint64_t *>(&area->done[ju].pad[kDoneExtra]), extra,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          }
+          // phase stamps (10-ns ticks from the poll that found the request; the
+          // host folds them into adl_bloom_probe_server_phases at the slot's
+          // next request, and prints them for a slow one under ADL_BLOOM_DEBUG):
+          // {seq, gap since the previous poll}, {poll loads back, slot staged},
+          // {hashed, bits read}, {answer stored, seq}, {the poll's start and the
+          // answer's store on the kernel's clock (low 32 bits), the host
+          // relates them to its own clock to place a slow request's delay}
+          const uint64_t ta = now_ticks();
+          uint64_t *dg = reinterpret_cast<uint64_t *>(&area->done[ju].pad[0]);
+          auto w2 = [](uint64_t a, uint64_t b) { return (uint64_t)(uint32_t)a | ((uint64_t)(uint32_t)b << 32); };
+          __hip_atomic_store(dg + 0, w2(seq, tp - tprev), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(dg + 1, w2(t_polled - tp, t_stage - tp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(dg + 2, w2(t_hash - tp, t_reads - tp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(dg + 4, w2(tp, ta), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(dg + 3, w2(ta - tp, seq), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+      };
+      uint32_t fan = 0;
+      {
+        const uint32_t u = lane / adl_srv::kMaxQ, q = lane % adl_srv::kMaxQ;
+        uint32_t j = kSlots;  // the slot lane 8u + q serves (kSlots: none)
+#pragma unroll
+        for (uint32_t x = 0; x < kGroup; ++x) j = u == x ? js[x] : j;
+        Prep pr{0ull, 0u, 0u, 0u, 0u};
+        const uint32_t bj = (uint32_t)__shfl((int)bell, (int)(j < kSlots ? j : 0u));
+        bool is_fan = false;
+        if (j < kSlots && (bj & kInlineBit)) {
+          if (q == 0) pr = prep_line(lline, j & (kInlineSlots - 1));
+        } else if (j < kSlots) {
+          const Slot &sl = *reinterpret_cast<const Slot *>(lslot[u]);
+          is_fan = sl.form == kFormFan;
+          if (!is_fan && q < min(sl.n, adl_srv::kMaxQ)) pr = prep_slot_query(sl, q);
+        }
+        const uint64_t fb = __ballot(is_fan && q == 0);  // bit 8u
+#pragma unroll
+        for (uint32_t x = 0; x < kGroup; ++x) fan |= (uint32_t)((fb >> (x * adl_srv::kMaxQ)) & 1u) << x;
+        serve(pr, fan, 0u);
+      }
+      // the group's slots in the fan form (wave-uniform), each served by the whole wave
+      for (uint32_t rest = fan; rest; rest &= rest - 1) {
+        const uint32_t x = (uint32_t)__builtin_ctz(rest);
+        const FanSlot &fs = *reinterpret_cast<const FanSlot *>(lslot[x]);
+        Prep pr{0ull, 0u, 0u, 0u, 0u};
+        if (lane < min(fs.n, adl_srv::kFanTables)) pr = prep_fan(fs, lane);
+        serve(pr, fan, x + 1u);
       }
       __syncthreads();  // the group's LDS copy is read before the next group overwrites it
     }
@@ -411,7 +498,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(16))) void probe
   // the last poll's answers are out: the host may launch the next kernel (on
   // the other stream) as soon as it sees this
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-  if (lane == 0) __hip_atomic_store(&area->ctl.gen_done, gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (lane0 == 0) __hip_atomic_store(&area->ctl.gen_done, gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 }  // namespace
@@ -588,10 +675,22 @@ void stop_all_at_exit() {
   }
 }
 
-bool answered(const Server *s, uint32_t my, uint32_t seq, uint32_t *bits) {
-  const uint32_t w = __atomic_load_n(&s->host->done[my].tagged, __ATOMIC_ACQUIRE);
-  if ((w >> 8) != (seq & 0xFFFFFFu)) return false;
-  *bits = w & 0xFFu;
+// The answer bits of request `seq` of slot `my`, once every word that holds
+// any of its `nans` answers carries its tag (word 1: answers 0-7; a fan
+// request's 8-15 and 16-23: the two extra words).  Each word is judged by its
+// own tag, so the order in which the kernel's stores arrive does not matter.
+bool answered(const Server *s, uint32_t my, uint32_t seq, uint32_t nans, uint32_t *bits) {
+  const Done &d = s->host->done[my];
+  const uint32_t tag = seq & 0xFFFFFFu;
+  const uint32_t w = __atomic_load_n(&d.tagged, __ATOMIC_ACQUIRE);
+  if ((w >> 8) != tag) return false;
+  uint32_t b = w & 0xFFu;
+  for (uint32_t i = 0; 8 * (i + 1) < nans; ++i) {
+    const uint32_t x = __atomic_load_n(&d.pad[kDoneExtra + i], __ATOMIC_ACQUIRE);
+    if ((x >> 8) != tag) return false;
+    b |= (x & 0xFFu) << (8 * (i + 1));
+  }
+  *bits = b;
   return true;
 }
 
@@ -625,7 +724,7 @@ int launch_next(Server *s) {
 //    published its generation (its last answers are out by then), then
 //    launch the next one unless that last poll answered the request.
 // *done = answered.
-int ensure_running(Server *s, uint32_t my, uint32_t seq, uint32_t *bits, bool *done) {
+int ensure_running(Server *s, uint32_t my, uint32_t seq, uint32_t nans, uint32_t *bits, bool *done) {
   *done = false;
   if (s->launched) {
     hipEvent_t ev = s->exited[s->gen % Server::kEvents];
@@ -659,7 +758,7 @@ int ensure_running(Server *s, uint32_t my, uint32_t seq, uint32_t *bits, bool *d
         }
       }
     }
-    if (answered(s, my, seq, bits)) {
+    if (answered(s, my, seq, nans, bits)) {
       *done = true;
       return ADL_OK;
     }
@@ -786,18 +885,31 @@ uint32_t live_servers() {
   return g_reg ? (uint32_t)g_reg->size() : 0u;
 }
 
-int probe(Server *s, const uint8_t *h_keys, const uint64_t *h_offsets, uint32_t key_stride, uint64_t n,
-          const uint64_t *range, const uint8_t *kq, uint64_t arena_epoch, uint8_t *h_out) {
-  const uint64_t key_bytes = h_offsets ? h_offsets[n] - h_offsets[0] : n * (uint64_t)key_stride;
-  if (!s || !eligible(n, key_bytes)) return ADL_ERR_INVALID_ARG;
-  // a slot per thread and server (round-robin); threads beyond kSlots share
-  // one in turn.  A thread remembers its slot for the server it used last.
+namespace {
+
+// A slot per thread and server (round-robin); threads beyond kSlots share one
+// in turn.  A thread remembers its slot for the server it used last, and
+// posts its requests of either form into that one slot.
+uint32_t thread_slot(Server *s) {
   thread_local uint64_t my_server = 0;
   thread_local uint32_t my = 0;
   if (my_server != s->id) {
     my = s->next_slot.fetch_add(1) % kSlots;
     my_server = s->id;
   }
+  return my;
+}
+
+// One request of the calling thread, whatever its form: the thread's slot, the
+// sequence number, the bell, the alive / relaunch protocol, the answer wait
+// (kBusy past kTimeout), the successor request and the phase folding.
+// may_inline: the request fits a bell line (it is inline when the thread's
+// slot has one).  write(my, seq, inl) puts the request into line `my` (inl) or
+// slot `my`, before the bell is rung.  nans: its answers, *bits (bit t: answer
+// t) on ADL_OK.
+template <class Write>
+int request(Server *s, bool may_inline, uint32_t nans, uint64_t arena_epoch, uint32_t *bits_out, Write &&write) {
+  const uint32_t my = thread_slot(s);
   std::lock_guard<std::mutex> slot_guard(s->slot_mu[my]);
   fold_phases(s->host, my, s->last_bell[my], s->last_seen[my]);
   // 30-bit sequence numbers, never 0 (the initial done); bit 31 of the bell
@@ -810,42 +922,19 @@ int probe(Server *s, const uint8_t *h_keys, const uint64_t *h_offsets, uint32_t 
   }
   s->seq[my] = (s->seq[my] + 1) & kSeqMask;
   if (s->seq[my] == 0) s->seq[my] = 1;
-  const bool inl = my < kInlineSlots && n == 1 && key_bytes <= kInlineKeyBytes && range[1] >= range[0] &&
-                   range[1] - range[0] <= 0xFFFFFFFFull;
+  const bool inl = my < kInlineSlots && may_inline;
   // the arena changed since the wave last invalidated its caches (or every
   // request invalidates: ADL_BLOOM_SERVER_INVALIDATE=1, round 5's behaviour)
   const bool inv = s->invalidate_always || arena_epoch > s->inv_epoch.load(std::memory_order_acquire);
   const uint32_t seq = s->seq[my] | (inl ? kInlineBit : 0u) | (inv ? kInvalidateBit : 0u);
   s->last_bell[my] = seq;
   const auto tw0 = std::chrono::steady_clock::now();
-  const uint8_t *kp = h_keys + (h_offsets ? h_offsets[0] : 0);
-  if (inl) {
-    // the whole line, check word last computed, in one copy; then the bell
-    Line ln{};
-    ln.seq = seq;
-    ln.k_klen = kq[0] | (uint32_t)key_bytes << 8;
-    ln.len = (uint32_t)(range[1] - range[0]);
-    ln.begin = range[0];
-    memcpy(ln.key, kp, key_bytes);
-    uint32_t w[16];
-    memcpy(w, &ln, sizeof(ln));
-    uint32_t x = kLineCheck;
-    for (uint32_t i = 0; i < 16; ++i) x ^= line_word_hash(w[i], i);
-    ln.check = x;
-    memcpy(&s->host->line[my], &ln, sizeof(ln));
-  } else {
-    Slot &sl = s->host->slot[my];
-    sl.n = (uint32_t)n;
-    sl.key_bytes = (uint32_t)key_bytes;
-    for (uint64_t q = 0; q < n; ++q) {
-      sl.range[2 * q] = range[2 * q];
-      sl.range[2 * q + 1] = range[2 * q + 1];
-      sl.kq[q] = kq[q];
-      sl.koff[q] = (uint16_t)(h_offsets ? h_offsets[q] - h_offsets[0] : q * key_stride);
-    }
-    sl.koff[n] = (uint16_t)key_bytes;
-    memcpy(sl.keys, kp, key_bytes);
-  }
+  // The extra answer words are written by fan requests only, so one left by
+  // an earlier fan request of this slot could carry this request's 24-bit tag
+  // again (2^24 requests later): give them a tag that is not this one's.
+  for (uint32_t i = 0; 8 * (i + 1) < nans; ++i)
+    __atomic_store_n(&s->host->done[my].pad[kDoneExtra + i], ~seq << 8, __ATOMIC_RELAXED);
+  write(my, seq, inl);
   // bell, then alive, both sequentially consistent (the kernel clears alive
   // and then polls once more: probe_server_kernel)
   __atomic_store_n(&s->host->bell[my], seq, __ATOMIC_SEQ_CST);
@@ -863,7 +952,7 @@ int probe(Server *s, const uint8_t *h_keys, const uint64_t *h_offsets, uint32_t 
     std::unique_lock<std::mutex> g(s->launch_mu, std::try_to_lock);
     if (g.owns_lock()) {
       const uint32_t gen0 = s->gen;
-      if (int rc = ensure_running(s, my, seq, &bits, &done)) return rc;
+      if (int rc = ensure_running(s, my, seq, nans, &bits, &done)) return rc;
       relaunched = s->gen != gen0;
     }
   }
@@ -877,7 +966,7 @@ int probe(Server *s, const uint8_t *h_keys, const uint64_t *h_offsets, uint32_t 
   std::chrono::steady_clock::time_point tl = t0;
   double max_gap_us = 0;
   while (!done) {
-    if (answered(s, my, seq, &bits)) break;
+    if (answered(s, my, seq, nans, &bits)) break;
     if (s->debug) {
       const auto tn = std::chrono::steady_clock::now();
       max_gap_us = std::max(max_gap_us, std::chrono::duration<double, std::micro>(tn - tl).count());
@@ -889,7 +978,7 @@ int probe(Server *s, const uint8_t *h_keys, const uint64_t *h_offsets, uint32_t 
     // check the kernel; past kTimeout the caller probes by a launch instead
     if (since() > std::chrono::microseconds(50)) {
       std::lock_guard<std::mutex> g(s->launch_mu);
-      if (int rc = ensure_running(s, my, seq, &bits, &done)) return rc;
+      if (int rc = ensure_running(s, my, seq, nans, &bits, &done)) return rc;
     }
     if (since() > kTimeout) return kBusy;
   }
@@ -948,7 +1037,76 @@ int probe(Server *s, const uint8_t *h_keys, const uint64_t *h_offsets, uint32_t 
   g_phases.host_ns.fetch_add(
       (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tw0).count(),
       std::memory_order_relaxed);
+  *bits_out = bits;
+  return ADL_OK;
+}
+
+}  // namespace
+
+int probe(Server *s, const uint8_t *h_keys, const uint64_t *h_offsets, uint32_t key_stride, uint64_t n,
+          const uint64_t *range, const uint8_t *kq, uint64_t arena_epoch, uint8_t *h_out) {
+  const uint64_t key_bytes = h_offsets ? h_offsets[n] - h_offsets[0] : n * (uint64_t)key_stride;
+  if (!s || !eligible(n, key_bytes)) return ADL_ERR_INVALID_ARG;
+  const bool may_inline =
+      n == 1 && key_bytes <= kInlineKeyBytes && range[1] >= range[0] && range[1] - range[0] <= 0xFFFFFFFFull;
+  const uint8_t *kp = h_keys + (h_offsets ? h_offsets[0] : 0);
+  uint32_t bits = 0;
+  const int rc = request(s, may_inline, (uint32_t)n, arena_epoch, &bits, [&](uint32_t my, uint32_t seq, bool inl) {
+    if (inl) {
+      // the whole line, check word last computed, in one copy; then the bell
+      Line ln{};
+      ln.seq = seq;
+      ln.k_klen = kq[0] | (uint32_t)key_bytes << 8;
+      ln.len = (uint32_t)(range[1] - range[0]);
+      ln.begin = range[0];
+      memcpy(ln.key, kp, key_bytes);
+      uint32_t w[16];
+      memcpy(w, &ln, sizeof(ln));
+      uint32_t x = kLineCheck;
+      for (uint32_t i = 0; i < 16; ++i) x ^= line_word_hash(w[i], i);
+      ln.check = x;
+      memcpy(&s->host->line[my], &ln, sizeof(ln));
+    } else {
+      Slot &sl = s->host->slot[my];
+      sl.n = (uint32_t)n;
+      sl.form = 0;  // (the slot's previous request may have been a fan request)
+      sl.key_bytes = (uint32_t)key_bytes;
+      for (uint64_t q = 0; q < n; ++q) {
+        sl.range[2 * q] = range[2 * q];
+        sl.range[2 * q + 1] = range[2 * q + 1];
+        sl.kq[q] = kq[q];
+        sl.koff[q] = (uint16_t)(h_offsets ? h_offsets[q] - h_offsets[0] : q * key_stride);
+      }
+      sl.koff[n] = (uint16_t)key_bytes;
+      memcpy(sl.keys, kp, key_bytes);
+    }
+  });
+  if (rc != ADL_OK) return rc;
   for (uint64_t q = 0; q < n; ++q) h_out[q] = (uint8_t)((bits >> q) & 1u);
+  return ADL_OK;
+}
+
+bool eligible_fan(uint64_t n, uint64_t key_bytes) { return n >= 1 && n <= kFanTables && key_bytes <= kFanKeyBytes; }
+
+int probe_fan(Server *s, const uint8_t *h_key, uint64_t key_bytes, uint32_t n, const uint64_t *range,
+              const uint8_t *kq, uint64_t arena_epoch, uint8_t *h_out) {
+  if (!s || !eligible_fan(n, key_bytes)) return ADL_ERR_INVALID_ARG;
+  uint32_t bits = 0;
+  const int rc = request(s, false, n, arena_epoch, &bits, [&](uint32_t my, uint32_t, bool) {
+    FanSlot &fs = *reinterpret_cast<FanSlot *>(&s->host->slot[my]);
+    fs.n = n;
+    fs.form = kFormFan;
+    fs.key_bytes = (uint32_t)key_bytes;
+    for (uint32_t t = 0; t < n; ++t) {
+      const uint64_t b0 = range[2 * t], b1 = range[2 * t + 1];
+      fs.e[t].begin = b0;
+      fs.e[t].len = b1 > b0 ? (uint32_t)std::min<uint64_t>(b1 - b0, 0xFFFFFFFFull) : 0u;
+      fs.e[t].k = kq[t];
+    }
+    if (key_bytes) memcpy(fs.key, h_key, key_bytes);
+  });
+  if (rc != ADL_OK) return rc;
+  for (uint32_t t = 0; t < n; ++t) h_out[t] = (uint8_t)((bits >> t) & 1u);
   return ADL_OK;
 }
 

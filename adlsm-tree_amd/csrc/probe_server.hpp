@@ -6,10 +6,15 @@
 
 #include <chrono>
 
+#include "../../include/adl_bloom.h"
+
 namespace adl_srv {
 
 constexpr uint32_t kMaxQ = 8;           // queries per request
 constexpr uint32_t kMaxKeyBytes = 320;  // key bytes per request
+// the fan form of a request: one key against up to kFanTables filter ranges
+constexpr uint32_t kFanTables = ADL_BLOOM_GET_MAX_TABLES;
+constexpr uint32_t kFanKeyBytes = ADL_BLOOM_GET_MAX_KEY_BYTES;
 // probe()'s answer wait before it gives up and returns kBusy (the caller then
 // probes by a launch; the request may still be served later, reading only the
 // cache arena, and its answer is ignored: each request has its own sequence)
@@ -34,6 +39,16 @@ __attribute__((visibility("hidden"))) bool eligible(uint64_t n, uint64_t key_byt
 __attribute__((visibility("hidden"))) int probe(Server *s, const uint8_t *h_keys, const uint64_t *h_offsets,
                                                 uint32_t key_stride, uint64_t n, const uint64_t *range,
                                                 const uint8_t *kq, uint64_t arena_epoch, uint8_t *h_out);
+
+// A fan request: ONE key (hashed once by the wave) against n filter ranges,
+// table t the device byte range [range[2t], range[2t+1]) of kq[t]-probe bits;
+// h_out[t] the answer.  One slot, one bell, one answer line; never inline.
+// Everything else -- the thread's slot, the sequence numbers, arena_epoch, the
+// statuses and kBusy -- is probe's.
+__attribute__((visibility("hidden"))) bool eligible_fan(uint64_t n, uint64_t key_bytes);
+__attribute__((visibility("hidden"))) int probe_fan(Server *s, const uint8_t *h_key, uint64_t key_bytes, uint32_t n,
+                                                    const uint64_t *range, const uint8_t *kq, uint64_t arena_epoch,
+                                                    uint8_t *h_out);
 
 // Servers that exist in this process (created, not destroyed).
 __attribute__((visibility("hidden"))) uint32_t live_servers();

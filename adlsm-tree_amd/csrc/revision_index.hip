@@ -292,6 +292,26 @@ int adl_bloom_revision_stats(const adl_bloom_revision *rev, uint32_t *num_levels
   return ADL_OK;
 }
 
+// One key looked up in every non-empty level's host index, level 0 first: no
+// device copy is made or used, nothing is allocated.
+int adl_bloom_revision_candidates_host(const adl_bloom_revision *rev, const uint8_t *h_key, uint64_t key_len,
+                                       int64_t seq, uint32_t *h_table, uint32_t capacity, uint32_t *num) {
+  if (!rev || !num || (key_len && !h_key) || (capacity && !h_table)) return ADL_ERR_INVALID_ARG;
+  const std::string_view u(key_len ? reinterpret_cast<const char *>(h_key) : "", key_len);
+  uint32_t n = 0;
+  for (size_t l = 0; l < rev->levels.size(); ++l) {
+    const adl_bloom_level *lv = rev->levels[l];
+    if (!lv || lv->ix.num_tables == 0) continue;
+    const uint32_t base = rev->table_base[l];
+    adl_level::LookupOne(lv->ix, u, seq, [&](uint32_t t) {
+      if (n < capacity) h_table[n] = base + t;
+      ++n;
+    });
+  }
+  *num = n;
+  return ADL_OK;
+}
+
 uint64_t adl_bloom_revision_candidates_workspace_bytes(const adl_bloom_revision *rev, uint64_t num_keys) {
   if (!rev) return 0;
   uint64_t a, b, c, d;

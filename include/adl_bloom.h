@@ -585,6 +585,57 @@ int adl_bloom_revision_read_plan(adl_bloom_revision *rev, adl_bloom_filter_cache
                                  uint64_t entry_capacity, uint64_t *num_hits, uint64_t pair_capacity,
                                  uint64_t *num_pairs, uint64_t *h_uncached, void *stream);
 
+/* ------------------------------------------- single-key revision Get */
+
+/* DB::Get of one key is Revision::Get: every level's candidate tables asked
+ * about the same key.  Up to ADL_BLOOM_GET_MAX_TABLES tables and a key of up
+ * to ADL_BLOOM_GET_MAX_KEY_BYTES bytes travel in ONE request to the cache's
+ * resident probe server (the key staged and hashed once, one lane per table,
+ * one answer line, no launch); anything larger, and any request the server
+ * does not take (switched off, missing, backing off, no answer in time), is
+ * one launched fan-out probe with the same answers. */
+#define ADL_BLOOM_GET_MAX_TABLES 24
+#define ADL_BLOOM_GET_MAX_KEY_BYTES 96
+
+/* One key against filter `filter` of every listed table: h_out[t] (num_tables
+ * bytes) and *h_uncached are by definition those of
+ * adl_bloom_filter_cache_probe_fanout for one key whose candidate list is
+ * tables 0 .. num_tables-1 -- a table that is not cached answers 1 and is
+ * counted, a filter the block does not have answers 0, each table is probed
+ * with the k of its own block.  The tables are resolved and pinned for the
+ * call as that call pins them.  num_tables == 0 does nothing.  h_key may be
+ * NULL for key_len == 0.  Synchronous. */
+int adl_bloom_filter_cache_probe_key(adl_bloom_filter_cache *cache, const char *const *oids,
+                                     const uint64_t *oid_lens, uint32_t num_tables, uint32_t filter,
+                                     const uint8_t *h_key, uint64_t key_len, uint8_t *h_out, uint64_t *h_uncached,
+                                     void *stream);
+
+/* GPU-free: the key's candidate tables over all levels, as global ids in
+ * Revision::Get's visiting order -- what adl_bloom_revision_candidates_device
+ * gives for this key at `seq` -- from the levels' host indices.  *num is the
+ * total; entries from `capacity` on are not written (h_table may be NULL for
+ * capacity == 0). */
+int adl_bloom_revision_candidates_host(const adl_bloom_revision *rev, const uint8_t *h_key, uint64_t key_len,
+                                       int64_t seq, uint32_t *h_table, uint32_t capacity, uint32_t *num);
+
+/* adl_bloom_revision_multiget for one key: the tables the Get still has to
+ * read, as global ids in visiting order, in h_hit_table; *num_hits above
+ * hit_capacity is ADL_ERR_WORKSPACE with *num_hits (and *num_candidates) set
+ * and nothing else written; a level created without oids or a NULL rev, cache,
+ * num_hits (or h_key with key_len > 0, or h_hit_table with hit_capacity > 0)
+ * is ADL_ERR_INVALID_ARG.  The candidates are selected on the host
+ * (adl_bloom_revision_candidates_host), ONLY their oids are resolved and
+ * pinned in `cache`, and they are probed by one
+ * adl_bloom_filter_cache_probe_key-style request; no device copy of the
+ * revision or its levels is made.  *num_candidates (optional): the candidate
+ * tables; *h_uncached (optional): the hits whose table was not cached.
+ * Nothing is allocated per call once the calling thread's scratch has grown.
+ * Synchronous. */
+int adl_bloom_revision_get(adl_bloom_revision *rev, adl_bloom_filter_cache *cache, uint32_t filter,
+                           const uint8_t *h_key, uint64_t key_len, int64_t seq, uint32_t *h_hit_table,
+                           uint32_t hit_capacity, uint32_t *num_hits, uint32_t *num_candidates, uint32_t *h_uncached,
+                           void *stream);
+
 /* ------------------------------------------- write-through builds into the cache */
 
 /* A table's filter block built straight into a reserved range of the cache
