@@ -60,6 +60,8 @@ EXPORTS = (
     "adl_bloom_revision_multiget",
     "adl_bloom_hits_by_table_workspace_bytes", "adl_bloom_hits_by_table_device", "adl_bloom_revision_read_plan",
     "adl_bloom_filter_cache_probe_key", "adl_bloom_revision_candidates_host", "adl_bloom_revision_get",
+    "adl_bloom_probe_batch_k_workspace_bytes", "adl_bloom_probe_batch_k_device",
+    "adl_bloom_filter_cache_probe_batch_workspace_bytes", "adl_bloom_filter_cache_probe_batch_device",
 )
 
 # one resident-server request holds a single-key Get of up to this many tables and key bytes
@@ -162,6 +164,13 @@ def lib() -> ctypes.CDLL:
         "adl_bloom_probe_device": (ctypes.c_int, [vp, vp, u64, u32, i32, vp, u64, vp, vp]),
         "adl_bloom_probe_batch_workspace_bytes": (u64, [u64, u32, i32, u32]),
         "adl_bloom_probe_batch_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, i32, vp, vp, u64, vp]),
+        "adl_bloom_probe_batch_k_workspace_bytes": (u64, [u64, u32, u32, u32]),
+        "adl_bloom_probe_batch_k_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, vp, vp, u32, vp, vp, u64,
+                                                           vp]),
+        "adl_bloom_filter_cache_probe_batch_workspace_bytes": (u64, [vp, ctypes.POINTER(ctypes.c_char_p), vp, u32, u64,
+                                                                     u32]),
+        "adl_bloom_filter_cache_probe_batch_device": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_char_p), vp, u32, u32,
+                                                                      vp, vp, u64, u32, vp, vp, vp, vp, u64, vp]),
         "adl_bloom_probe_multi_device": (ctypes.c_int, [vp, vp, u64, u32, vp, u32, vp, vp, i32, vp, vp]),
         "adl_bloom_probe": (ctypes.c_int, [vp, vp, u64, u32, i32, vp, u64, vp, vp]),
         "adl_bloom_filter_set_create": (ctypes.c_int, [vp, vp, u32, i32, ctypes.POINTER(vp)]),
@@ -560,6 +569,37 @@ def probe_batch(keys, filter_id, bitmaps, bitmap_off, offsets=None, bits_per_key
     return out[:n]
 
 
+def probe_batch_k(keys, filter_id, bitmaps, bitmap_off, filter_k, max_k: int, offsets=None, stream=None,
+                  bitmap_end=None, out=None, workspace=None):
+    """probe_batch with a probe count per filter (adl_bloom_probe_batch_k_device): filter f
+    probes filter_k[f] bits (a uint8 device tensor, one entry per filter, each in [1, max_k]);
+    max_k, a host value in 1..30, bounds them and sizes the plan.  Batches, paths and answers
+    as probe_batch; a batch whose max_k is above ADL_BLOOM_PROBE_BATCH_MAX_K (default 2; 30: no
+    limit) stays on the direct kernel.  `workspace`: an optional uint8 device tensor to use instead of one from torch's
+    caching allocator (ADL_ERR_WORKSPACE if the call's plan needs more)."""
+    pk, po, n, stride = _keyset(keys, offsets)
+    F = bitmap_off.numel() - (0 if bitmap_end is not None else 1)
+    if filter_k.dtype != _torch().uint8 or filter_k.numel() < F or not filter_k.is_contiguous():
+        raise ValueError("filter_k must be a contiguous uint8 tensor of one entry per filter")
+    L = lib()
+    if workspace is None:
+        wsb = L.adl_bloom_probe_batch_k_workspace_bytes(n, F, max_k, stride)
+        with _on(stream):
+            workspace = empty_device(wsb, keys.device)
+    else:
+        wsb = workspace.numel()
+    if out is None:
+        with _on(stream):
+            out = _torch().empty(max(n, 1), dtype=_torch().uint8, device=keys.device)
+    elif out.dtype != _torch().uint8 or out.numel() < n or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor of at least n elements")
+    _check(L.adl_bloom_probe_batch_k_device(pk, po, n, stride, _dptr(filter_id), F, _dptr(bitmaps),
+                                            _dptr(bitmap_off), _dptr(bitmap_end), _dptr(filter_k), max_k,
+                                            _dptr(out), _dptr(workspace), wsb, _stream(stream)),
+           "adl_bloom_probe_batch_k_device")
+    return out[:n]
+
+
 def murmur3_batch(keys, offsets=None, seed_a=SEED1, seed_b=SEED2, stream=None):
     pk, po, n, stride = _keyset(keys, offsets)
     with _on(stream):
@@ -761,6 +801,50 @@ class FilterCache:
                                                   out.ctypes.data, ctypes.byref(unc), _host_stream(stream)),
                "adl_bloom_filter_cache_probe")
         return out[:n], unc.value
+
+    def probe_batch_workspace_bytes(self, oids, n: int, key_stride: int) -> int:
+        """The workspace probe_batch_device needs for n queries over `oids` as they are cached now
+        (key_stride 0: keys with offsets)."""
+        arr = (ctypes.c_char_p * max(len(oids), 1))(*oids)
+        lens = np.array([len(o) for o in oids] or [0], dtype=np.uint64)
+        return lib().adl_bloom_filter_cache_probe_batch_workspace_bytes(self._h, arr, lens.ctypes.data, len(oids), n,
+                                                                        key_stride)
+
+    def probe_batch_device_status(self, oids, table, keys, offsets=None, filter: int = 0, stream=None, out=None,
+                                  workspace=None):
+        """probe_batch_device that returns (status, out, cached) instead of raising."""
+        pk, po, n, stride = _keyset(keys, offsets)
+        arr = (ctypes.c_char_p * max(len(oids), 1))(*oids)
+        lens = np.array([len(o) for o in oids] or [0], dtype=np.uint64)
+        L = lib()
+        if workspace is None:
+            wsb = L.adl_bloom_filter_cache_probe_batch_workspace_bytes(self._h, arr, lens.ctypes.data, len(oids), n,
+                                                                       stride)
+            with _on(stream):
+                workspace = empty_device(wsb, keys.device)
+        else:
+            wsb = workspace.numel()
+        if out is None:
+            with _on(stream):
+                out = _torch().empty(max(n, 1), dtype=_torch().uint8, device=keys.device)
+        elif out.dtype != _torch().uint8 or out.numel() < n or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 tensor of at least n elements")
+        cached = np.zeros(max(len(oids), 1), dtype=np.uint8)
+        rc = L.adl_bloom_filter_cache_probe_batch_device(self._h, arr, lens.ctypes.data, len(oids), filter, pk, po, n,
+                                                         stride, _dptr(table), _dptr(out), cached.ctypes.data,
+                                                         _dptr(workspace), wsb, _stream(stream))
+        return rc, out[:n], cached[:len(oids)]
+
+    def probe_batch_device(self, oids, table, keys, offsets=None, filter: int = 0, stream=None, out=None,
+                           workspace=None):
+        """Bulk probe of DEVICE keys (adl_bloom_filter_cache_probe_batch_device): query i against filter `filter`
+        of table oids[table[i]] (`table`: a uint32 device tensor), each table with the k of its own block, through
+        the tile-binned pipeline when the batch is large.  Returns (0/1 uint8 device tensor, per-table cached
+        flags as a numpy array); the answers are probe()'s, and an index >= len(oids) answers 0.  The call
+        returns after the probe has completed on `stream`."""
+        rc, out, cached = self.probe_batch_device_status(oids, table, keys, offsets, filter, stream, out, workspace)
+        _check(rc, "adl_bloom_filter_cache_probe_batch_device")
+        return out, cached
 
     def probe_fanout(self, oids, pair_begin, pair_table, keys: np.ndarray, offsets=None, filter: int = 0,
                      stream=None):

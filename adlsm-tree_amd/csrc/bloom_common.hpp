@@ -198,6 +198,16 @@ namespace adl_host {
 // 2^20 queries, at least 18 % faster from 2^22 on.
 constexpr uint64_t kProbeBatchVarMinDefault = 1ull << 22;
 
+// The largest max_k at which the binned probe with a probe count per filter
+// takes a batch.  A binned query costs k_f entries whether it is a member or
+// not, while the direct kernel stops at the first clear bit: at 2^24 queries
+// over 256 filters of 1 M keys the pipeline beat the direct kernel on an
+// all-member and on an all-absent batch at max_k = 2 only; from 6 on it won
+// the member batch (x 0.39-0.52) and lost the absent one (x 1.07-1.31)
+// (profiles/probe_batch_k/).  At 10^8 queries it won both kinds
+// at every max_k from 6 on: a caller with such batches sets the knob to 30.
+constexpr uint32_t kProbeBatchMaxKDefault = 2;
+
 // Tuning and test switches, read from the environment once per
 // process.  adl_bloom_reload_knobs() reads them again (tests, between calls:
 // no call of the library may be running).
@@ -223,7 +233,11 @@ struct Knobs {
   // probe pipeline (probe_binned.hip).  0: never; 1 .. 2^20 mean 2^20 (the
   // pipeline's own floor).  Not set: kProbeBatchVarMinDefault.
   uint64_t probe_batch_var_min = kProbeBatchVarMinDefault;
-  bool debug = false;             // ADL_BLOOM_DEBUG: the plan and failing HIP calls to stderr
+  // ADL_BLOOM_PROBE_BATCH_MAX_K: a batch with a probe count per filter
+  // (adl_bloom_probe_batch_k_device) whose max_k is above this stays on the
+  // direct kernel.  Not set: kProbeBatchMaxKDefault.
+  uint32_t probe_batch_max_k = kProbeBatchMaxKDefault;
+  bool debug = false;            // ADL_BLOOM_DEBUG: the plan and failing HIP calls to stderr
   uint32_t exp = 0, pb_exp = 0;   // ADL_BLOOM_EXP / ADL_PB_EXP: diagnostics build (make stamps) only
 
   void load() {
@@ -246,6 +260,7 @@ struct Knobs {
     server_invalidate = u64("ADL_BLOOM_SERVER_INVALIDATE", 0) != 0;
     probe_batch_var_min = u64("ADL_BLOOM_PROBE_BATCH_VAR_MIN", kProbeBatchVarMinDefault);
     if (probe_batch_var_min) probe_batch_var_min = std::max<uint64_t>(probe_batch_var_min, 1ull << 20);
+    probe_batch_max_k = (uint32_t)std::min<uint64_t>(u64("ADL_BLOOM_PROBE_BATCH_MAX_K", kProbeBatchMaxKDefault), 30);
     debug = u64("ADL_BLOOM_DEBUG", 0) != 0;
 #ifdef ADL_BLOOM_STAMPS
     exp = (uint32_t)u64("ADL_BLOOM_EXP", 0);
@@ -518,6 +533,13 @@ __attribute__((visibility("hidden"))) int adl_probe_ranges_device_ev(
     const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n, uint32_t key_stride, const uint32_t *d_filter_id,
     uint32_t num_filters, const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end,
     const uint8_t *d_k, uint8_t *d_out, hipStream_t st, hipEvent_t done);
+
+// Library-internal (bloom_probe.hip): the direct multi-filter probe with a
+// probe count per filter (d_k[f]); d_end null: filter f ends at d_begin[f + 1].
+__attribute__((visibility("hidden"))) int adl_probe_multi_k_device(
+    const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n, uint32_t key_stride, const uint32_t *d_filter_id,
+    uint32_t num_filters, const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end,
+    const uint8_t *d_k, uint8_t *d_out, hipStream_t st);
 
 // The same for adl_bloom_probe_fanout_device (d_k[f]: filter f's probe count).
 __attribute__((visibility("hidden"))) int adl_probe_fanout_device_ev(

@@ -526,6 +526,19 @@ int adl_host::adl_probe_ranges_device_ev(const uint8_t *d_keys, const uint64_t *
                      st, d_end, done, d_k);
 }
 
+// The direct kernel with a probe count per filter over offsets (d_end null)
+// or ranges: what a batch of adl_bloom_probe_batch_k_device that does not take
+// the binned pipeline runs.
+int adl_host::adl_probe_multi_k_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n,
+                                       uint32_t key_stride, const uint32_t *d_filter_id, uint32_t num_filters,
+                                       const uint8_t *d_bitmaps, const uint64_t *d_begin, const uint64_t *d_end,
+                                       const uint8_t *d_k, uint8_t *d_out, hipStream_t st) {
+  if (n == 0) return ADL_OK;
+  if (!d_keys || !d_filter_id || !d_out || (num_filters && !d_k)) return ADL_ERR_INVALID_ARG;
+  return probe_multi(d_keys, d_offsets, n, key_stride, d_filter_id, 0, num_filters, d_bitmaps, d_begin, 10, d_out,
+                     st, d_end, nullptr, d_k);
+}
+
 extern "C" int adl_bloom_probe_ranges_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n,
                                              uint32_t key_stride, const uint32_t *d_filter_id,
                                              uint32_t num_filters, const uint8_t *d_bitmaps,

@@ -393,6 +393,36 @@ RC FilterCache::ProbeFanout(const vector<string_view> &oids, const vector<uint32
   return FromStatus(st);
 }
 
+uint64_t FilterCache::ProbeBatchWorkspaceBytes(const vector<string_view> &oids, uint64_t n, uint32_t key_stride) {
+  if (!h_) return 0;
+  vector<const char *> ptr(oids.size());
+  vector<uint64_t> len(oids.size());
+  for (size_t j = 0; j < oids.size(); ++j) {
+    ptr[j] = oids[j].data();
+    len[j] = oids[j].size();
+  }
+  return adl_bloom_filter_cache_probe_batch_workspace_bytes(h_, ptr.data(), len.data(), (uint32_t)oids.size(), n,
+                                                            key_stride);
+}
+
+RC FilterCache::ProbeBatchDevice(const vector<string_view> &oids, int filter, const uint8_t *d_keys,
+                                 const uint64_t *d_offsets, uint64_t n, uint32_t key_stride, const uint32_t *d_table,
+                                 uint8_t *d_out, vector<uint8_t> *cached, void *d_workspace, uint64_t workspace_bytes,
+                                 void *stream) {
+  if (cached) cached->assign(oids.size(), 0);
+  if (!h_) return status_;
+  if (filter < 0) return OUT_OF_RANGE;
+  vector<const char *> ptr(oids.size());
+  vector<uint64_t> len(oids.size());
+  for (size_t j = 0; j < oids.size(); ++j) {
+    ptr[j] = oids[j].data();
+    len[j] = oids[j].size();
+  }
+  return FromStatus(adl_bloom_filter_cache_probe_batch_device(
+      h_, ptr.data(), len.data(), (uint32_t)oids.size(), (uint32_t)filter, d_keys, d_offsets, n, key_stride, d_table,
+      d_out, cached ? cached->data() : nullptr, d_workspace, workspace_bytes, stream));
+}
+
 FilterCache *FilterCache::Shared(int) { return Shared(); }
 
 FilterCache *FilterCache::Shared() {

@@ -229,6 +229,20 @@ class FilterCache {
    * and hashed once each (one launch, adl_bloom_filter_cache_probe_fanout). */
   RC ProbeFanout(const vector<string_view> &oids, const vector<uint32_t> &begin, const vector<uint32_t> &table,
                  const KeyArena &keys, int filter, vector<uint8_t> &out, uint64_t *uncached = nullptr);
+  /* Bulk probe of keys that are already on the DEVICE
+   * (adl_bloom_filter_cache_probe_batch_device): d_out[i] (device, n bytes) is
+   * Probe's answer for key i against table oids[d_table[i]] (device u32; an
+   * index past the list answers 0), each table with the k of its own block,
+   * through the tile-binned pipeline when the batch is large.  d_offsets
+   * null: keys of key_stride bytes.  cached (optional): 1 per listed table
+   * that was cached.  The workspace comes from ProbeBatchWorkspaceBytes for
+   * the same list, n and stride (0 with offsets); DEVICE_ERROR if a table was
+   * replaced by one of a larger k since (ask again).  Returns after the probe
+   * has completed on `stream`. */
+  uint64_t ProbeBatchWorkspaceBytes(const vector<string_view> &oids, uint64_t n, uint32_t key_stride);
+  RC ProbeBatchDevice(const vector<string_view> &oids, int filter, const uint8_t *d_keys, const uint64_t *d_offsets,
+                      uint64_t n, uint32_t key_stride, const uint32_t *d_table, uint8_t *d_out,
+                      vector<uint8_t> *cached, void *d_workspace, uint64_t workspace_bytes, void *stream = nullptr);
   /* The process-wide cache FilterBlockReader::Init(string_view) keeps its
    * bitmaps in, for blocks of every bits_per_key (arena
    * ADL_BLOOM_READER_CACHE_BYTES, default 1 GiB); created on first use and

@@ -582,6 +582,69 @@ int adl_bloom_filter_cache_probe(adl_bloom_filter_cache *c, const char *const *o
   }
 }
 
+uint64_t adl_bloom_filter_cache_probe_batch_workspace_bytes(adl_bloom_filter_cache *c, const char *const *oids,
+                                                            const uint64_t *oid_lens, uint32_t num_tables, uint64_t n,
+                                                            uint32_t key_stride) {
+  if (!c || (num_tables && (!oids || !oid_lens))) return 0;
+  try {
+    uint32_t max_k = 1;  // (an uncached table is the all-ones filter with k = 1)
+    {
+      std::lock_guard<std::mutex> g(c->mu);
+      std::string key;
+      for (uint32_t j = 0; j < num_tables; ++j) {
+        key.assign(oids[j], oid_lens[j]);
+        auto it = c->index.find(key);
+        if (it != c->index.end()) max_k = std::max<uint32_t>(max_k, it->second->k);
+      }
+    }
+    return adl_bloom_probe_batch_k_workspace_bytes(n, num_tables, max_k, key_stride);
+  } catch (...) {
+    return 0;
+  }
+}
+
+// The bulk probe of device keys: the listed tables resolved and pinned as by
+// every cached probe, their range and k tables staged and uploaded, and
+// adl_bloom_probe_batch_k_device over the arena with max_k the largest k
+// resolved.  The stream is idle when the pins are given back, on every path.
+int adl_bloom_filter_cache_probe_batch_device(adl_bloom_filter_cache *c, const char *const *oids,
+                                              const uint64_t *oid_lens, uint32_t num_tables, uint32_t filter,
+                                              const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n,
+                                              uint32_t key_stride, const uint32_t *d_table, uint8_t *d_out,
+                                              uint8_t *h_cached, void *d_workspace, uint64_t workspace_bytes,
+                                              void *stream) {
+  if (!c || (num_tables && (!oids || !oid_lens))) return ADL_ERR_INVALID_ARG;
+  if (n && (!d_keys || !d_table || !d_out || (!d_offsets && key_stride == 0))) return ADL_ERR_INVALID_ARG;
+  try {
+    hipStream_t st = (hipStream_t)stream;  // (the caller's keys are ordered on it)
+    Resolved &res = t_res;
+    PinScope pins(c, res);
+    resolve_tables(c, oids, oid_lens, num_tables, filter, res);
+    if (h_cached && num_tables) memcpy(h_cached, res.cached.data(), num_tables);
+    if (n == 0) return ADL_OK;
+    uint32_t max_k = 1;
+    for (uint8_t k : res.kt) max_k = std::max<uint32_t>(max_k, k);
+    adl_host::StagePlan plan;
+    const TableBlock tb(plan, res);
+    adl_host::Staging &sg = adl_host::t_stage;
+    plan.take(1);  // (a list of no tables still has an address)
+    if (int rc = sg.reserve(plan.end, plan.end)) return rc;
+    tb.fill(sg.host, res);
+    if (hipMemcpyAsync(sg.dev, sg.host, plan.end, hipMemcpyHostToDevice, st) != hipSuccess) {
+      (void)hipStreamSynchronize(st);
+      return ADL_ERR_DEVICE;
+    }
+    // (a short workspace is refused before the pipeline's first launch: d_out is not written)
+    const int rc = adl_bloom_probe_batch_k_device(d_keys, d_offsets, n, key_stride, d_table, num_tables, c->arena,
+                                                  tb.begin(sg.dev), tb.begin(sg.dev) + num_tables, tb.k(sg.dev),
+                                                  max_k, d_out, d_workspace, workspace_bytes, st);
+    if (hipStreamSynchronize(st) != hipSuccess) return ADL_ERR_DEVICE;
+    return rc;
+  } catch (...) {
+    return ADL_ERR_OUT_OF_MEMORY;
+  }
+}
+
 int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *c, const char *const *oids, const uint64_t *oid_lens,
                                         uint32_t num_tables, uint32_t filter, const uint8_t *h_keys,
                                         const uint64_t *h_offsets, uint64_t num_keys, uint32_t key_stride,

@@ -36,6 +36,10 @@
 //       so the racing stores of different tiles agree)
 //   K6  per block: the block's answers gathered run by run into LDS, then
 //       out[i] = answer at the query's place (coalesced throughout)
+// adl_bloom_probe_batch_k_device runs the same pipeline with a probe count per
+// filter (blocks written under different bits_per_key): K0 keeps filter f's
+// k_f in its descriptor, the plan is the one for max_k (the bound on every
+// k_f), and P1 writes k_f entries per query into a chunk's max_k * C region.
 // Algorithmic traffic per query: 16 B key + 4 B id + 1 B answer; the
 // pipeline moves ~130 B of streaming traffic per query instead of ~4.4
 // random 64-B requests.
@@ -75,7 +79,8 @@ struct PFilter {
   uint32_t qbase;       // first slot in filter order (K2b)
   uint32_t chunk_base;  // first chunk (K2b)
   uint32_t nchunks;     // (K2b)
-  uint32_t pad_[3];
+  uint32_t k;           // its own probe count in [1, max_k] (K0; a call with a k per filter only, else 0)
+  uint32_t pad_[2];
   uint64_t byte_off;    // bitmap start in the arena (K0)
   uint64_t table_base;  // first (tile, chunk) table entry (K2b)
 };
@@ -83,7 +88,7 @@ static_assert(sizeof(PFilter) == 64, "PFilter is 64 B");
 
 struct Plan {
   uint64_t n = 0;
-  uint32_t F = 0, k = 0, C = 0, nb = 0;
+  uint32_t F = 0, k = 0, C = 0, nb = 0;  // k: the probe count, or the largest one of a call with a k per filter
   uint64_t maxch = 0;
   // workspace byte offsets
   uint32_t ng = 0;  // groups of kScanGroup blocks (K2)
@@ -93,11 +98,14 @@ struct Plan {
 
 constexpr uint32_t kScanGroup = 64;  // blocks per column-sum group (K2)
 
-Plan make_plan(uint64_t n, uint32_t F, int32_t bpk, bool pairs) {
+// k: every filter's probe count, or the bound max_k of a call with a k per
+// filter: chunk c's entry region is then k * C words at c * k * C, of which a
+// chunk of filter f fills the first k_f * (its queries).
+Plan make_plan_k(uint64_t n, uint32_t F, uint32_t k, bool pairs) {
   Plan p;
   p.n = n;
   p.F = F;
-  p.k = (uint32_t)adl_host::num_probes(bpk);
+  p.k = k;
   // chunk size: k*C entries + the tile histogram fit one workgroup's LDS
   const uint32_t room = kLdsWords - (kMaxTiles + 4) - 64;
   p.C = std::min<uint32_t>(kMaxC, (room / p.k) & ~63u);
@@ -127,9 +135,31 @@ Plan make_plan(uint64_t n, uint32_t F, int32_t bpk, bool pairs) {
   return p;
 }
 
+Plan make_plan(uint64_t n, uint32_t F, int32_t bpk, bool pairs) {
+  return make_plan_k(n, F, (uint32_t)adl_host::num_probes(bpk), pairs);
+}
+
+// What the size functions promise for k: the largest plan of any k' <= k.  C
+// is quantised ((room / k) & ~63), so k * C, and with it a plan of many
+// filters and few queries, is not monotone in k (4096 filters, 2^20 queries:
+// the plan of k = 12 is 0.1 % smaller than that of 11).  A workspace sized for
+// k then serves every call with a smaller one: the filter cache sizes for the
+// largest k among its tables now, and a table replaced by one of a smaller k
+// must not make the workspace short.  The calls themselves ask only for their
+// own plan.
+uint64_t promised_bytes(uint64_t n, uint32_t F, uint32_t k, bool pairs) {
+  uint64_t most = 0;
+  for (uint32_t kk = 1; kk <= k; ++kk) most = std::max(most, make_plan_k(n, F, kk, pairs).total);
+  return most + 256;
+}
+
 // ---------------------------------------------------------------- K0
+// filter_k (null: one k for the call): filter f's own probe count, clamped
+// into [1, max_k] so that no chunk writes outside its max_k * C entry words
+// whatever the array holds.
 __global__ __launch_bounds__(kBlk) void pb_desc_kernel(const uint64_t *__restrict__ off,
                                                        const uint64_t *__restrict__ end, uint32_t F,
+                                                       const uint8_t *__restrict__ filter_k, uint32_t max_k,
                                                        PFilter *__restrict__ desc, uint32_t *__restrict__ scal) {
   __shared__ uint32_t scratch[kBlk / kWave + 1];
   uint32_t carry = 0;
@@ -149,6 +179,7 @@ __global__ __launch_bounds__(kBlk) void pb_desc_kernel(const uint64_t *__restric
         d.tiles = (d.m + (1u << kTL) - 1) >> kTL;
         d.byte_off = b0;
       }
+      if (filter_k) d.k = min(max((uint32_t)filter_k[f], 1u), max_k);
     }
     uint32_t total;
     const uint32_t pre = block_excl_scan<kBlk>(f <= F ? d.tiles : 0u, scratch, &total);
@@ -229,6 +260,15 @@ __global__ __launch_bounds__(kBlk) void pb_colsum_kernel(const uint32_t *__restr
 // workgroup of its own (and the workgroups after it none).
 constexpr uint64_t kTileWork = kTileBytes / 4;
 
+// PERK: a probe count per filter (desc[f].k).  A tile's entries are then
+// weighted by its own filter's k: lq holds the entries before each filter
+// (k_f x queries) in units of kWUnit entries, each filter's rounded up, instead
+// of the queries before it, and the split weighs a unit kWUnit where it
+// weighed a query k.  (Under 30 * 2^31 entries: 32 to a unit, plus one unit a
+// filter, fit 32 bits; the rounding is nothing beside kTileWork.)
+constexpr uint32_t kWUnit = 32;
+
+template <bool PERK>
 __global__ __launch_bounds__(kBlk) void pb_plan_kernel(uint32_t *__restrict__ gsum, uint32_t ng, uint32_t F,
                                                        uint32_t C, uint64_t maxch, PFilter *__restrict__ desc,
                                                        uint32_t *__restrict__ chunk_filter,
@@ -236,9 +276,10 @@ __global__ __launch_bounds__(kBlk) void pb_plan_kernel(uint32_t *__restrict__ gs
                                                        uint32_t *__restrict__ split) {
   __shared__ uint32_t scratch[kBlk / kWave + 1];
   __shared__ uint64_t red[kBlk / kWave];
-  __shared__ uint32_t ltb[kMaxBucketFilters + 1], lq[kMaxBucketFilters + 1];  // tile_base, qbase
+  __shared__ uint32_t ltb[kMaxBucketFilters + 1], lq[kMaxBucketFilters + 1];  // tile_base, qbase (PERK: entry units)
   const uint64_t stride = F + 1;
   uint64_t cq = 0, cc = 0, ct = 0;  // running query / chunk / table-entry starts over filter blocks
+  uint32_t cw = 0;                  // PERK: running entry units
   for (uint32_t f0 = 0; f0 <= F; f0 += kBlk) {
     const uint32_t f = f0 + threadIdx.x;
     uint32_t tot = 0;
@@ -264,6 +305,10 @@ __global__ __launch_bounds__(kBlk) void pb_plan_kernel(uint32_t *__restrict__ gs
     const uint32_t pq = block_excl_scan<kBlk>(f <= F ? tot : 0u, scratch, &all_q);
     const uint32_t pc = block_excl_scan<kBlk>(nc, scratch, &all_c);
     const uint64_t te = (uint64_t)(tiles + 1) * nc;
+    uint32_t all_w = 0, pw = 0;
+    if constexpr (PERK)
+      pw = block_excl_scan<kBlk>(f < F ? (uint32_t)(((uint64_t)desc[f].k * tot + kWUnit - 1) / kWUnit) : 0u, scratch,
+                                 &all_w);
     // 64-bit exclusive scan of the table entries: wave sums, then the waves before
     const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     uint64_t incl = te;
@@ -281,7 +326,7 @@ __global__ __launch_bounds__(kBlk) void pb_plan_kernel(uint32_t *__restrict__ gs
     __syncthreads();
     if (f <= F) {
       ltb[f] = desc[f].tile_base;
-      lq[f] = (uint32_t)(cq + pq);
+      lq[f] = PERK ? cw + pw : (uint32_t)(cq + pq);
       desc[f].cnt = tot;
       desc[f].qbase = (uint32_t)(cq + pq);
       desc[f].chunk_base = (uint32_t)(cc + pc);
@@ -293,14 +338,16 @@ __global__ __launch_bounds__(kBlk) void pb_plan_kernel(uint32_t *__restrict__ gs
     cq += all_q;
     cc += all_c;
     ct += all_t;
+    cw += all_w;
   }
   __syncthreads();
   for (uint64_t j = cc + threadIdx.x; j < maxch; j += kBlk) chunk_filter[j] = kSentinel;
   // the work before tile t of filter f (filters in order, a filter's queries
   // spread evenly over its tiles)
+  const uint32_t kw = PERK ? kWUnit : k;
   auto work = [&](uint32_t f, uint32_t t) -> uint64_t {
     const uint32_t tiles = ltb[f + 1] - ltb[f], q = lq[f + 1] - lq[f];
-    return kTileWork * (ltb[f] + t) + (uint64_t)k * (lq[f] + (tiles ? (uint64_t)t * q / tiles : 0u));
+    return kTileWork * (ltb[f] + t) + (uint64_t)kw * (lq[f] + (tiles ? (uint64_t)t * q / tiles : 0u));
   };
   const uint64_t wtot = work(F, 0);  // (filter F, the out-of-range bucket, has no tiles)
   for (uint32_t s = threadIdx.x; s <= G; s += kBlk) {
@@ -472,12 +519,18 @@ __global__ __launch_bounds__(kBlk) void pb_scatter_kernel(Src src, const uint32_
 // the first clear bit, src/filter_block.cpp:54-59; the answer is the AND
 // either way, and a two-round form measured slower: HISTORY.md).  KFIX = 0:
 // runtime k.
-template <int KFIX>
-__global__ __launch_bounds__(kBlk) void pb_bin_kernel(const uint2 *__restrict__ hs, const PFilter *__restrict__ desc,
-                                                      const uint32_t *__restrict__ chunk_filter,
-                                                      const uint32_t *__restrict__ scal, uint32_t k, uint32_t C,
-                                                      uint32_t *__restrict__ ent, uint32_t *__restrict__ table,
-                                                      uint8_t *__restrict__ res, uint32_t exp) {
+//
+// PERK: a probe count per filter.  `k` is then the call's max_k, which only
+// places a chunk's entry region (c * k * C); a chunk of filter f takes its k
+// from the descriptor and fills the first k_f x (its queries) words of the
+// region (k_f <= max_k: pb_desc_kernel).  KFIX > 0 with PERK: the chunks of
+// filters with k_f == KFIX take the unrolled path, the others the runtime one.
+template <int KFIX, bool PERK>
+__device__ __forceinline__ void pb_bin_body(const uint2 *__restrict__ hs, const PFilter *__restrict__ desc,
+                                            const uint32_t *__restrict__ chunk_filter,
+                                            const uint32_t *__restrict__ scal, uint32_t k, uint32_t C,
+                                            uint32_t *__restrict__ ent, uint32_t *__restrict__ table,
+                                            uint8_t *__restrict__ res, uint32_t exp) {
 #ifndef ADL_BLOOM_STAMPS
   exp = 0;  // diagnostics build only (wrong answers): 64 no entry stores, 128 no scatter (count only), 256 no count
 #endif
@@ -485,7 +538,6 @@ __global__ __launch_bounds__(kBlk) void pb_bin_kernel(const uint2 *__restrict__ 
   uint32_t *hist = lds;                          // kMaxTiles + 1 counters, later cursors
   uint32_t *scratch = lds + kMaxTiles + 4;       // scan scratch (64 words)
   uint32_t *lpos = scratch + 64;                 // k*C sorted entries
-  const uint32_t kk = KFIX > 0 ? (uint32_t)KFIX : k;
   constexpr int KR = KFIX > 0 ? KFIX : 1;
   const int tid = threadIdx.x;
   const uint32_t total_chunks = scal[1];
@@ -515,6 +567,7 @@ __global__ __launch_bounds__(kBlk) void pb_bin_kernel(const uint2 *__restrict__ 
     const uint32_t q0 = d.qbase + j * C;
     const uint32_t cnt = min(C, d.cnt - j * C);
     const uint32_t T = d.tiles;
+    const uint32_t kk = PERK ? d.k : KFIX > 0 ? (uint32_t)KFIX : k;
     const FastMod mod{d.m, d.magic, d.shift, 0u};
     __syncthreads();  // the previous chunk's entries are read out of lpos
     for (uint32_t t = tid; t <= T; t += kBlk) hist[t] = 0;
@@ -551,11 +604,14 @@ __global__ __launch_bounds__(kBlk) void pb_bin_kernel(const uint2 *__restrict__ 
       for (uint32_t v = (nvec << 2) + tid; v < total; v += kBlk) dst[v] = lpos[v];
       continue;
     }
+    // the unrolled path: every chunk of a fixed-k call, the chunks of k_f == KFIX of a call with a k per filter
+    // (uniform over the workgroup: one chunk, one filter)
+    const bool fix = KFIX > 0 && (!PERK || kk == (uint32_t)KFIX);
     uint32_t pos[kCPT][KR];
 #pragma unroll
     for (uint32_t r = 0; r < kCPT; ++r) {
       if (live[r]) {
-        if constexpr (KFIX > 0) {
+        if (fix) {
 #pragma unroll
           for (int jj = 0; jj < KFIX; ++jj) {
             pos[r][jj] = fastmod(cur[r].x + (uint32_t)jj * cur[r].y, mod);
@@ -575,8 +631,8 @@ __global__ __launch_bounds__(kBlk) void pb_bin_kernel(const uint2 *__restrict__ 
     for (uint32_t r = 0; r < kCPT; ++r) {
       const uint32_t q = tid + r * kBlk;
       if (live[r] && !(exp & 128)) {
-        if constexpr (KFIX > 0) {
-          uint32_t sl[KFIX];
+        if (fix) {
+          uint32_t sl[KR];
 #pragma unroll
           for (int jj = 0; jj < KFIX; ++jj) sl[jj] = atomicAdd(&hist[pos[r][jj] >> kTL], 1u);
 #pragma unroll
@@ -598,6 +654,27 @@ __global__ __launch_bounds__(kBlk) void pb_bin_kernel(const uint2 *__restrict__ 
     for (uint32_t v = tid; v < nvec; v += kBlk) dst4[v] = src4[v];
     for (uint32_t v = (nvec << 2) + tid; v < total; v += kBlk) dst[v] = lpos[v];
   }
+}
+
+template <int KFIX>
+__global__ __launch_bounds__(kBlk) void pb_bin_kernel(const uint2 *__restrict__ hs, const PFilter *__restrict__ desc,
+                                                      const uint32_t *__restrict__ chunk_filter,
+                                                      const uint32_t *__restrict__ scal, uint32_t k, uint32_t C,
+                                                      uint32_t *__restrict__ ent, uint32_t *__restrict__ table,
+                                                      uint8_t *__restrict__ res, uint32_t exp) {
+  pb_bin_body<KFIX, false>(hs, desc, chunk_filter, scal, k, C, ent, table, res, exp);
+}
+
+// A probe count per filter (max_k in place of k).  KFIX as pb_bin_body's.
+template <int KFIX>
+__global__ __launch_bounds__(kBlk) void pb_bin_perk_kernel(const uint2 *__restrict__ hs,
+                                                           const PFilter *__restrict__ desc,
+                                                           const uint32_t *__restrict__ chunk_filter,
+                                                           const uint32_t *__restrict__ scal, uint32_t max_k,
+                                                           uint32_t C, uint32_t *__restrict__ ent,
+                                                           uint32_t *__restrict__ table, uint8_t *__restrict__ res,
+                                                           uint32_t exp) {
+  pb_bin_body<KFIX, true>(hs, desc, chunk_filter, scal, max_k, C, ent, table, res, exp);
 }
 
 // ---------------------------------------------------------------- P2
@@ -993,6 +1070,20 @@ bool var_eligible(uint64_t n, uint32_t F) {
 
 bool keys16_eligible(uint64_t n, uint32_t F) { return n >= kMinBinned && filters_and_size_ok(n, F); }
 
+// the key shape as the debug lines name it
+const char *shape_name(Shape shape, bool binned, uint32_t key_stride, char *buf, size_t len) {
+  if (shape == Shape::kStride || (shape == Shape::kKeys16 && !binned))
+    snprintf(buf, len, "stride %u", key_stride);
+  else
+    snprintf(buf, len, "%s", shape == Shape::kVar ? "var" : "keys16");
+  return buf;
+}
+
+int run_binned(const Plan &p, Shape shape, const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_stride,
+               const uint32_t *d_filter_id, const uint8_t *d_bitmaps, const uint64_t *d_bitmap_off,
+               const uint64_t *d_bitmap_end, const uint8_t *d_filter_k, uint8_t *d_out, void *d_workspace,
+               uint64_t workspace_bytes, hipStream_t st);
+
 }  // namespace
 
 extern "C" {
@@ -1003,7 +1094,7 @@ uint64_t adl_bloom_probe_batch_workspace_bytes(uint64_t n, uint32_t num_filters,
   const bool k16 = key_stride == 16;  // (an unaligned pointer is not seen here: such a batch needs no more than this)
   if (!(k16 ? keys16_eligible(n, num_filters) : var_eligible(n, num_filters)))
     return 256;  // the direct kernel: no workspace
-  return make_plan(n, num_filters, bits_per_key, !k16).total + 256;
+  return promised_bytes(n, num_filters, (uint32_t)adl_host::num_probes(bits_per_key), !k16);
 }
 
 int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n, uint32_t key_stride,
@@ -1023,11 +1114,8 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
   const uint32_t k_dbg = (uint32_t)adl_host::num_probes(bits_per_key);
   if (adl_host::knobs().debug) {
     char what[32];
-    if (shape == Shape::kStride || (shape == Shape::kKeys16 && !binned))
-      snprintf(what, sizeof what, "stride %u", key_stride);
-    else
-      snprintf(what, sizeof what, "%s", shape == Shape::kVar ? "var" : "keys16");
-    fprintf(stderr, "adl_bloom probe_batch: %s (%s), k=%u, launches=%d\n", binned ? "binned" : "direct", what, k_dbg,
+    fprintf(stderr, "adl_bloom probe_batch: %s (%s), k=%u, launches=%d\n", binned ? "binned" : "direct",
+            shape_name(shape, binned, key_stride, what, sizeof what), k_dbg,
             binned ? (shape == Shape::kKeys16 ? 9 : 10) : 1);
   }
   if (!binned) {
@@ -1038,6 +1126,61 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
                                         d_bitmap_off, bits_per_key, d_out, stream);
   }
   const Plan p = make_plan(n, num_filters, bits_per_key, shape != Shape::kKeys16);
+  return run_binned(p, shape, d_keys, d_offsets, key_stride, d_filter_id, d_bitmaps, d_bitmap_off, d_bitmap_end,
+                    nullptr, d_out, d_workspace, workspace_bytes, st);
+}
+
+uint64_t adl_bloom_probe_batch_k_workspace_bytes(uint64_t n, uint32_t num_filters, uint32_t max_k,
+                                                 uint32_t key_stride) {
+  if (max_k < 1 || max_k > 30) return 0;
+  const bool k16 = key_stride == 16;
+  if (max_k > adl_host::knobs().probe_batch_max_k ||
+      !(k16 ? keys16_eligible(n, num_filters) : var_eligible(n, num_filters)))
+    return 256;  // the direct kernel: no workspace
+  return promised_bytes(n, num_filters, max_k, !k16);
+}
+
+int adl_bloom_probe_batch_k_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n, uint32_t key_stride,
+                                   const uint32_t *d_filter_id, uint32_t num_filters, const uint8_t *d_bitmaps,
+                                   const uint64_t *d_bitmap_off, const uint64_t *d_bitmap_end,
+                                   const uint8_t *d_filter_k, uint32_t max_k, uint8_t *d_out, void *d_workspace,
+                                   uint64_t workspace_bytes, void *stream) {
+  if (n == 0) return ADL_OK;
+  if (!d_keys || !d_filter_id || !d_out || max_k < 1 || max_k > 30) return ADL_ERR_INVALID_ARG;
+  if (num_filters && (!d_bitmaps || !d_bitmap_off || !d_filter_k)) return ADL_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const Shape shape = d_offsets ? Shape::kVar : key_stride == 16 ? Shape::kKeys16 : Shape::kStride;
+  bool binned = max_k <= adl_host::knobs().probe_batch_max_k;  // (a query costs k_f entries, hit or miss: DESIGN.md §5)
+  if (shape == Shape::kKeys16)
+    binned = binned && reinterpret_cast<uintptr_t>(d_keys) % 16 == 0 && keys16_eligible(n, num_filters);
+  else
+    binned = binned && (shape == Shape::kVar || key_stride != 0) && var_eligible(n, num_filters);
+  if (adl_host::knobs().debug) {
+    char what[32];
+    fprintf(stderr, "adl_bloom probe_batch_k: %s (%s), kmax=%u, launches=%d\n", binned ? "binned" : "direct",
+            shape_name(shape, binned, key_stride, what, sizeof what), max_k,
+            binned ? (shape == Shape::kKeys16 ? 9 : 10) : 1);
+  }
+  if (!binned)
+    return adl_host::adl_probe_multi_k_device(d_keys, d_offsets, n, key_stride, d_filter_id, num_filters, d_bitmaps,
+                                              d_bitmap_off, d_bitmap_end, d_filter_k, d_out, st);
+  const Plan p = make_plan_k(n, num_filters, max_k, shape != Shape::kKeys16);
+  return run_binned(p, shape, d_keys, d_offsets, key_stride, d_filter_id, d_bitmaps, d_bitmap_off, d_bitmap_end,
+                    d_filter_k, d_out, d_workspace, workspace_bytes, st);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The pipeline's launches over a workspace laid out by `p`.  d_filter_k null:
+// every filter probes p.k bits; else filter f its own d_filter_k[f], clamped
+// into [1, p.k].
+int run_binned(const Plan &p, Shape shape, const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_stride,
+               const uint32_t *d_filter_id, const uint8_t *d_bitmaps, const uint64_t *d_bitmap_off,
+               const uint64_t *d_bitmap_end, const uint8_t *d_filter_k, uint8_t *d_out, void *d_workspace,
+               uint64_t workspace_bytes, hipStream_t st) {
+  const uint64_t n = p.n;
   if (!d_workspace || workspace_bytes < p.total + 256) return ADL_ERR_WORKSPACE;
   uint8_t *ws = reinterpret_cast<uint8_t *>(adl_host::round_up(reinterpret_cast<uintptr_t>(d_workspace), 256));
   PFilter *desc = reinterpret_cast<PFilter *>(ws + p.o_desc);
@@ -1052,7 +1195,7 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
   uint8_t *res = ws + p.o_res;
   uint32_t *split = reinterpret_cast<uint32_t *>(ws + p.o_split);
   uint2 *qh = reinterpret_cast<uint2 *>(ws + p.o_qh);  // (the new shapes only)
-  const uint32_t F = num_filters;
+  const uint32_t F = p.F;
   const uint32_t cus = adl_host::device_cus();
   const uint32_t g_tile = std::min(cus, kMaxSlots);  // pb_tile's workgroups
   const size_t lds_k1 = (size_t)(2 * F + 2) * 4;                       // counters + tile counts
@@ -1067,15 +1210,20 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
   constexpr uint32_t exp = 0;
 #endif
   try {
-    hipLaunchKernelGGL(pb_desc_kernel, dim3(1), dim3(kBlk), 0, st, d_bitmap_off, d_bitmap_end, F, desc, scal);
+    hipLaunchKernelGGL(pb_desc_kernel, dim3(1), dim3(kBlk), 0, st, d_bitmap_off, d_bitmap_end, F, d_filter_k, p.k, desc,
+                       scal);
     ADL_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(pb_hist_kernel, dim3(p.nb), dim3(kBlk), lds_k1, st, d_filter_id, n, F, p.nb, desc, cnt);
     ADL_HIP_TRY(hipGetLastError());
     uint32_t *gsum = reinterpret_cast<uint32_t *>(ws + p.o_gsum);
     hipLaunchKernelGGL(pb_colsum_kernel, dim3(p.ng), dim3(kBlk), 0, st, cnt, p.nb, F, gsum);
     ADL_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(pb_plan_kernel, dim3(1), dim3(kBlk), 0, st, gsum, p.ng, F, p.C, p.maxch, desc, cf, scal, p.k,
-                       g_tile, split);
+    if (d_filter_k)
+      hipLaunchKernelGGL(pb_plan_kernel<true>, dim3(1), dim3(kBlk), 0, st, gsum, p.ng, F, p.C, p.maxch, desc, cf, scal,
+                         p.k, g_tile, split);
+    else
+      hipLaunchKernelGGL(pb_plan_kernel<false>, dim3(1), dim3(kBlk), 0, st, gsum, p.ng, F, p.C, p.maxch, desc, cf, scal,
+                         p.k, g_tile, split);
     ADL_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(pb_starts_kernel, dim3(p.ng), dim3(kBlk), 0, st, cnt, gsum, p.nb, F, desc, start);
     ADL_HIP_TRY(hipGetLastError());
@@ -1111,8 +1259,11 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
       ADL_HIP_TRY(hipGetLastError());
       return ADL_OK;
     };
-    const int rc_bin = p.k == 6 ? bin(adl_host::lds_limit<pb_bin_kernel<6>>, pb_bin_kernel<6>)
-                                : bin(adl_host::lds_limit<pb_bin_kernel<0>>, pb_bin_kernel<0>);
+    // (a k per filter: p.k is max_k, and the chunks of k_f == 6 keep the unrolled path where max_k admits one)
+    const int rc_bin = d_filter_k ? (p.k >= 6 ? bin(adl_host::lds_limit<pb_bin_perk_kernel<6>>, pb_bin_perk_kernel<6>)
+                                              : bin(adl_host::lds_limit<pb_bin_perk_kernel<0>>, pb_bin_perk_kernel<0>))
+                       : p.k == 6 ? bin(adl_host::lds_limit<pb_bin_kernel<6>>, pb_bin_kernel<6>)
+                                  : bin(adl_host::lds_limit<pb_bin_kernel<0>>, pb_bin_kernel<0>);
     if (rc_bin != ADL_OK) return rc_bin;
     if (int rc = adl_host::lds_limit<pb_gather_kernel>()) return rc;
     hipLaunchKernelGGL(pb_gather_kernel, dim3(p.nb), dim3(kGatherBlk), lds_k6, st, dest, res, n, F, p.nb, cnt, start,
@@ -1124,4 +1275,4 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
   }
 }
 
-}  // extern "C"
+}  // namespace

@@ -247,7 +247,11 @@ int adl_bloom_probe_fanout_device(const uint8_t *d_keys, const uint64_t *d_offse
  * adl_bloom_probe_batch_workspace_bytes takes key_stride == 0 for
  * variable-length keys (what a caller with d_offsets passes) and returns 256
  * for a batch that stays on the direct kernel.  A batch that takes the
- * pipeline with less workspace than that returns ADL_ERR_WORKSPACE.
+ * pipeline with less workspace than its plan needs returns ADL_ERR_WORKSPACE.
+ * The size is the largest plan of any k up to num_probes(bits_per_key): the
+ * call's own plan wherever plans grow with k, and up to 1.1 % more where the
+ * quantised chunk size makes a plan of many filters and few queries step down
+ * (4096 filters, 2^20 queries); it never shrinks as k grows.
  * Read contract, as for every probe: d_keys at any alignment, and no byte
  * outside [d_keys + off(0), d_keys + off(n)) is read -- the hashing kernel
  * stages whole aligned 16-byte blocks only where they lie inside that range,
@@ -262,6 +266,38 @@ int adl_bloom_probe_batch_device(const uint8_t *d_keys, const uint64_t *d_offset
                                  const uint32_t *d_filter_id, uint32_t num_filters, const uint8_t *d_bitmaps,
                                  const uint64_t *d_bitmap_off, const uint64_t *d_bitmap_end, int32_t bits_per_key,
                                  uint8_t *d_out, void *d_workspace, uint64_t workspace_bytes, void *stream);
+
+/* adl_bloom_probe_batch_device with a probe count per filter (filter blocks
+ * written under different bits_per_key; the reference reads bpk per block,
+ * src/filter_block.cpp:158-170).  The plan is made from max_k, which bounds
+ * every filter's k: chunk size and entry regions are those of a uniform call
+ * with k = max_k, and a chunk of filter f fills k_f entries per query of its
+ * region.  So adl_bloom_probe_batch_k_workspace_bytes(n, F, k(bpk), stride) ==
+ * adl_bloom_probe_batch_workspace_bytes(n, F, bpk, stride), every array where
+ * the uniform plan has it, and a workspace sized for max_k serves every call
+ * with a smaller max_k.  Eligibility, the read contract, the filter edge
+ * cases (a 0-byte filter, one of 2^31 bits or more and an id >= num_filters
+ * answer 0), stream order and ADL_ERR_WORKSPACE are adl_bloom_probe_batch_device's;
+ * a batch that stays direct runs the direct kernel with d_filter_k, and the
+ * two paths answer bit for bit the same.  A batch whose max_k is above
+ * ADL_BLOOM_PROBE_BATCH_MAX_K (read again by adl_bloom_reload_knobs; 30: no
+ * limit; not set: 2, the measured crossover at 2^24 queries, DESIGN.md §5 and
+ * §8) stays direct as well, and its workspace size is 256; the size equation
+ * above holds for every max_k the knob admits.
+ *
+ * max_k in 1..30; key_stride as for adl_bloom_probe_batch_workspace_bytes.
+ * 256 for a batch that stays on the direct kernel; 0 for max_k outside 1..30. */
+uint64_t adl_bloom_probe_batch_k_workspace_bytes(uint64_t n, uint32_t num_filters,
+                                                 uint32_t max_k, uint32_t key_stride);
+
+/* adl_bloom_probe_batch_device with a probe count per filter: d_filter_k[f] (device,
+ * num_filters bytes, each in [1, max_k]; anything else is outside the contract, and the
+ * binned path clamps it so that nothing outside the workspace is written). */
+int adl_bloom_probe_batch_k_device(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n,
+                                   uint32_t key_stride, const uint32_t *d_filter_id, uint32_t num_filters,
+                                   const uint8_t *d_bitmaps, const uint64_t *d_bitmap_off,
+                                   const uint64_t *d_bitmap_end, const uint8_t *d_filter_k, uint32_t max_k,
+                                   uint8_t *d_out, void *d_workspace, uint64_t workspace_bytes, void *stream);
 
 /* Host-pointer convenience for adl_bloom_probe_device.  Synchronous. */
 int adl_bloom_probe(const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t n,
@@ -362,6 +398,31 @@ int adl_bloom_filter_cache_probe_fanout(adl_bloom_filter_cache *cache, const cha
                                         uint32_t key_stride, const uint32_t *h_pair_begin,
                                         const uint32_t *h_pair_table, uint8_t *h_out, uint64_t *h_uncached,
                                         void *stream);
+
+/* Bulk probe of DEVICE keys through the cache (a large existence check over
+ * the cached tables): adl_bloom_probe_batch_k_device over the arena, each table
+ * with the k of its own block, so a big batch takes the tile-binned pipeline.
+ *
+ * The workspace size for the largest k among the listed tables as they are
+ * cached now (an uncached table: k 1); key_stride as for
+ * adl_bloom_probe_batch_workspace_bytes. */
+uint64_t adl_bloom_filter_cache_probe_batch_workspace_bytes(adl_bloom_filter_cache *cache,
+        const char *const *oids, const uint64_t *oid_lens, uint32_t num_tables,
+        uint64_t n, uint32_t key_stride);
+
+/* Query i (DEVICE keys) probes filter `filter` of table d_table[i] (device u32, an index into the oid list).
+ * Answers are adl_bloom_filter_cache_probe's for the same queries: 1 for a table that is not cached,
+ * 0 for a filter the block does not have, 0 for an index >= num_tables, each table with the k of its own block.
+ * h_cached (optional, num_tables bytes): 1 where the table was cached.  d_out: n bytes on the device.
+ * The listed tables are resolved and pinned once, the range and k tables uploaded from the thread's staging,
+ * the probe enqueued on `stream`, and the call returns after it has completed (the pins are held until then).
+ * ADL_ERR_WORKSPACE: the workspace is smaller than this call's plan needs (a table was replaced by one of a
+ * larger k since the size was asked): d_out is not written, the pins are given back; ask the size again. */
+int adl_bloom_filter_cache_probe_batch_device(adl_bloom_filter_cache *cache, const char *const *oids,
+        const uint64_t *oid_lens, uint32_t num_tables, uint32_t filter,
+        const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n, uint32_t key_stride,
+        const uint32_t *d_table, uint8_t *d_out, uint8_t *h_cached,
+        void *d_workspace, uint64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------- resident level index */
 
