@@ -1291,6 +1291,15 @@ int make_plan(const uint64_t *counts, uint32_t nf, int32_t bpk, Plan &p) {
   const uint32_t cmax =
       std::min<uint32_t>(kBlockA * kpt, (lds_words_a - hist_words - 32 - 256) / (k + 1)) & ~3u;
   if (cmax < 4) return ADL_ERR_TOO_LARGE;
+  // ADL_BLOOM_CHUNK_KEYS (test override): a cap on the bound pick_c works
+  // under, at least 256 (the smallest C a plan picks of its own accord when
+  // the chunks fill less than one round) and at most the plan's own bound.
+  // Filters of a few thousand keys then have as many chunks as only filters
+  // of tens of millions have otherwise (pass B's segment batches).
+  auto cap_c = [&](uint32_t cm) -> uint32_t {
+    if (!kn.chunk_keys) return cm;
+    return std::min<uint32_t>(cm, std::max<uint32_t>(kn.chunk_keys, 256)) & ~3u;
+  };
   // chunks of C keys over all filters (each filter's last chunk is partial)
   auto nchunks = [&](uint64_t c) {
     uint64_t w = 0;
@@ -1333,7 +1342,7 @@ int make_plan(const uint64_t *counts, uint32_t nf, int32_t bpk, Plan &p) {
   if (claim && room_cl > 64) {
     const uint32_t cm = std::min<uint32_t>(kBlockA * kpt, (uint32_t)(room_cl * 100 / (kClaimSlack * k + 100))) & ~3u;
     if (cm >= 4) {
-      C = pick_c(cm);
+      C = pick_c(cap_c(cm));
       int64_t cw = std::min<int64_t>(room_cl - C, 36ll * kBlockA);  // <= 4 * VPT * BLOCK
       if (kn.claim_cap) cw = std::min<int64_t>(cw, (int64_t)k * C * std::max<uint32_t>(kn.claim_cap, 100) / 100 + 3);
       cap_cl = (uint32_t)cw & ~3u;
@@ -1349,7 +1358,7 @@ int make_plan(const uint64_t *counts, uint32_t nf, int32_t bpk, Plan &p) {
   } else {
     claim = false;
   }
-  if (!claim) C = pick_c(cmax);
+  if (!claim) C = pick_c(cap_c(cmax));
   p.a.nf = nf;
   p.a.stage_keys = 1;
   {

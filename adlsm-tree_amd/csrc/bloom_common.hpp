@@ -213,6 +213,7 @@ constexpr uint32_t kProbeBatchMaxKDefault = 2;
 // no call of the library may be running).
 struct Knobs {
   uint32_t tile_log2 = 0;         // ADL_BLOOM_TILE_LOG2: pass-B tile bits (10..20; 0: the plan's choice)
+  uint32_t chunk_keys = 0;        // ADL_BLOOM_CHUNK_KEYS: cap on pass A's keys per chunk (tests; 0: the plan's own)
   uint32_t claim = 3;             // ADL_BLOOM_CLAIM: 0 off, 1 wherever the share test passes, 2 forced, 3 auto
   uint32_t claim_cap = 0;         // ADL_BLOOM_CLAIM_CAP: claim region cap, percent of k*C (0: the LDS left)
   bool hash_dedup = true;         // ADL_BLOOM_HASH_DEDUP: pass A skips repeated hash pairs
@@ -247,6 +248,7 @@ struct Knobs {
     };
     *this = Knobs{};
     tile_log2 = (uint32_t)u64("ADL_BLOOM_TILE_LOG2", 0);
+    chunk_keys = (uint32_t)std::min<uint64_t>(u64("ADL_BLOOM_CHUNK_KEYS", 0), 1u << 20);
     claim = (uint32_t)u64("ADL_BLOOM_CLAIM", 3);
     claim_cap = (uint32_t)u64("ADL_BLOOM_CLAIM_CAP", 0);
     hash_dedup = u64("ADL_BLOOM_HASH_DEDUP", 1) != 0;
