@@ -62,7 +62,15 @@ EXPORTS = (
     "adl_bloom_filter_cache_probe_key", "adl_bloom_revision_candidates_host", "adl_bloom_revision_get",
     "adl_bloom_probe_batch_k_workspace_bytes", "adl_bloom_probe_batch_k_device",
     "adl_bloom_filter_cache_probe_batch_workspace_bytes", "adl_bloom_filter_cache_probe_batch_device",
+    "adl_bloom_stream_create", "adl_bloom_stream_destroy", "adl_bloom_stream_reset", "adl_bloom_stream_append",
+    "adl_bloom_stream_append_device", "adl_bloom_stream_cut", "adl_bloom_stream_counts",
+    "adl_bloom_stream_finish_workspace_bytes", "adl_bloom_stream_finish_device", "adl_bloom_stream_finish",
+    "adl_bloom_filter_cache_build_stream",
 )
+
+# keys per workgroup of the streamed build's append kernel for keys that are not aligned 16-byte keys
+# (include/adl_bloom.h: ADL_BLOOM_STREAM_RUN_KEYS)
+STREAM_RUN_KEYS = 512
 
 # one resident-server request holds a single-key Get of up to this many tables and key bytes
 # (include/adl_bloom.h: ADL_BLOOM_GET_MAX_TABLES, ADL_BLOOM_GET_MAX_KEY_BYTES)
@@ -195,6 +203,18 @@ def lib() -> ctypes.CDLL:
         "adl_bloom_probe_server_launches": (ctypes.c_int, [ctypes.POINTER(u64)]),
         "adl_bloom_probe_server_phases": (ctypes.c_int, [ctypes.POINTER(u64), ctypes.POINTER(u64),
                                                           ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
+        "adl_bloom_stream_create": (ctypes.c_int, [u64, ctypes.POINTER(vp)]),
+        "adl_bloom_stream_destroy": (ctypes.c_int, [vp]),
+        "adl_bloom_stream_reset": (ctypes.c_int, [vp]),
+        "adl_bloom_stream_append": (ctypes.c_int, [vp, vp, vp, u64, u32, vp]),
+        "adl_bloom_stream_append_device": (ctypes.c_int, [vp, vp, vp, u64, u32, vp]),
+        "adl_bloom_stream_cut": (ctypes.c_int, [vp]),
+        "adl_bloom_stream_counts": (ctypes.c_int, [vp, ctypes.POINTER(u32), vp, u32]),
+        "adl_bloom_stream_finish_workspace_bytes": (u64, [vp, i32]),
+        "adl_bloom_stream_finish_device": (ctypes.c_int, [vp, i32, u32, vp, vp, vp, u64, vp]),
+        "adl_bloom_stream_finish": (ctypes.c_int, [vp, i32, u32, vp, vp, vp]),
+        "adl_bloom_filter_cache_build_stream": (ctypes.c_int, [vp, vp, i32, u32, vp, u64, ctypes.POINTER(u64),
+                                                                ctypes.POINTER(vp), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -451,6 +471,97 @@ def build_segmented_host(keys, key_begin, out, bitmap_off, offsets=None, bits_pe
     else:
         _check(lib().adl_bloom_build_segmented(*args, _stream(stream)), "adl_bloom_build_segmented")
     return out
+
+
+class StreamBuilder:
+    """Streamed build (adl_bloom_stream): keys are appended in batches while a table fills
+    (FilterBlockWriter::Update) and hashed on arrival; finish() builds every filter from the stored
+    hash pairs (FilterBlockWriter::Final).  One thread at a time per object."""
+
+    def __init__(self, reserve_keys: int = 0):
+        self._h = ctypes.c_void_p()
+        _check(lib().adl_bloom_stream_create(int(reserve_keys), ctypes.byref(self._h)), "adl_bloom_stream_create")
+
+    def append_status(self, keys, offsets=None, stream=None) -> int:
+        """numpy arrays: a host batch (copied before the call returns); torch device tensors: a
+        device-resident batch.  keys (n, stride) uint8, or packed bytes with offsets (n + 1) uint64."""
+        L = lib()
+        if isinstance(keys, np.ndarray):
+            if offsets is None:
+                assert keys.ndim == 2 and keys.dtype == np.uint8 and keys.flags.c_contiguous
+                n, stride, po = keys.shape[0], keys.shape[1], None
+            else:
+                assert offsets.dtype == np.uint64 and offsets.flags.c_contiguous and keys.flags.c_contiguous
+                n, stride, po = len(offsets) - 1, 0, offsets.ctypes.data
+            return L.adl_bloom_stream_append(self._h, keys.ctypes.data, po, n, stride, _stream(stream))
+        pk, po, n, stride = _keyset(keys, offsets)
+        return L.adl_bloom_stream_append_device(self._h, pk, po, n, stride, _stream(stream))
+
+    def append(self, keys, offsets=None, stream=None) -> None:
+        _check(self.append_status(keys, offsets, stream), "adl_bloom_stream_append")
+
+    def cut(self) -> None:
+        _check(lib().adl_bloom_stream_cut(self._h), "adl_bloom_stream_cut")
+
+    def reset(self) -> None:
+        _check(lib().adl_bloom_stream_reset(self._h), "adl_bloom_stream_reset")
+
+    def counts(self) -> np.ndarray:
+        """key_begin of the filters so far (F + 1 entries; an open tail counts as a last filter)."""
+        nf = ctypes.c_uint32()
+        _check(lib().adl_bloom_stream_counts(self._h, ctypes.byref(nf), None, 0), "adl_bloom_stream_counts")
+        kb = np.zeros(nf.value + 1, dtype=np.uint64)
+        _check(lib().adl_bloom_stream_counts(self._h, ctypes.byref(nf), kb.ctypes.data, len(kb)),
+               "adl_bloom_stream_counts")
+        return kb
+
+    def workspace_bytes(self, bits_per_key: int = 10) -> int:
+        return lib().adl_bloom_stream_finish_workspace_bytes(self._h, bits_per_key)
+
+    def _layout(self, bits_per_key: int):
+        kb = self.counts()
+        counts = kb[1:] - kb[:-1]
+        sizes = np.array([bitmap_bytes(int(c), bits_per_key) for c in counts], dtype=np.uint64)
+        alloc = np.array([bitmap_alloc_bytes(int(c), bits_per_key) for c in counts], dtype=np.uint64)
+        if len(counts) and (sizes == 0).any():
+            raise AdlBloomError(-1 if bits_per_key < 0 else ADL_ERR_TOO_LARGE, "bitmap size")
+        boff = np.zeros(len(counts), dtype=np.uint64)
+        if len(counts) > 1:
+            boff[1:] = np.cumsum(alloc[:-1])
+        return boff, sizes, int(alloc.sum())
+
+    def finish(self, bits_per_key: int = 10, flags: int = 0, stream=None, device="cuda"):
+        """Every filter's bitmap from the stored pairs, as build_segmented returns them:
+        (device bitmaps buffer, host bitmap byte offsets (F), exact sizes (F)).  Enqueued on `stream`
+        behind every earlier append; does not synchronise (the workspace is allocated for `stream`)."""
+        boff, sizes, total = self._layout(bits_per_key)
+        ws_bytes = self.workspace_bytes(bits_per_key)
+        with _on(stream):
+            out = empty_device(total, device)
+            ws = empty_device(ws_bytes, device)
+        _check(lib().adl_bloom_stream_finish_device(self._h, bits_per_key, flags, _dptr(out), boff.ctypes.data,
+                                                    _dptr(ws), ws_bytes, _stream(stream)),
+               "adl_bloom_stream_finish_device")
+        return out, boff, sizes
+
+    def finish_host(self, out, bitmap_off, bits_per_key: int = 10, flags: int = 0, stream=None):
+        """Filter f's exact-length bitmap into out[bitmap_off[f]:] (host uint8 buffer, any alignment).
+        Synchronous."""
+        bo = np.ascontiguousarray(bitmap_off, dtype=np.uint64)
+        _check(lib().adl_bloom_stream_finish(self._h, bits_per_key, flags, _host_ptr(out), bo.ctypes.data,
+                                             _host_stream(stream)), "adl_bloom_stream_finish")
+        return out
+
+    def close(self) -> None:
+        if self._h:
+            lib().adl_bloom_stream_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def probe(keys, bitmap, nbytes: int | None = None, offsets=None, bits_per_key: int = 10, stream=None):
@@ -922,6 +1033,27 @@ class FilterCache:
         publish(ticket, oid) makes it resident under the table's oid, abandon(ticket) gives the range back."""
         rc, block, t = self.build_status(keys, key_begin, offsets, bits_per_key, flags, stream)
         _check(rc, "adl_bloom_filter_cache_build")
+        return block, t
+
+    def build_stream_status(self, sb: "StreamBuilder", bits_per_key: int = 10, flags: int = 0, stream=None):
+        """(status, block bytes or None, ticket or None) of adl_bloom_filter_cache_build_stream."""
+        nbytes = filter_block_bytes(sb.counts(), bits_per_key)
+        if nbytes == 0:
+            return (-1 if bits_per_key < 0 else ADL_ERR_TOO_LARGE), None, None
+        block = np.empty(nbytes, dtype=np.uint8)
+        h, got = ctypes.c_void_p(), ctypes.c_uint64()
+        rc = lib().adl_bloom_filter_cache_build_stream(self._h, sb._h, bits_per_key, flags, block.ctypes.data, nbytes,
+                                                       ctypes.byref(got), ctypes.byref(h), _host_stream(stream))
+        if rc != ADL_OK:
+            return rc, None, None
+        return rc, block[:got.value].tobytes(), FilterCache.Ticket(h)
+
+    def build_stream(self, sb: "StreamBuilder", bits_per_key: int = 10, flags: int = 0, stream=None):
+        """build() with a StreamBuilder as the key source: the filters of sb.counts() built from its hash
+        pairs into a reserved range of the arena (nothing is uploaded or hashed); returns (block: bytes,
+        ticket) for publish / abandon.  CACHE_VERIFY re-probes from the pairs.  `sb` is not consumed."""
+        rc, block, t = self.build_stream_status(sb, bits_per_key, flags, stream)
+        _check(rc, "adl_bloom_filter_cache_build_stream")
         return block, t
 
     def build_device(self, keys, key_begin, offsets=None, bits_per_key: int = 10, flags: int = 0, stream=None,

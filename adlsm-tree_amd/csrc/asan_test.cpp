@@ -209,6 +209,27 @@ void WriterChecks() {
   CHECK((int)file.size() == t.GetFileSize());
   CHECK(file.size() > 18 && (unsigned char)file[file.size() - 2] == 0x12 &&
         (unsigned char)file[file.size() - 1] == 0x34);  // footer magic (src/footer_block.cpp:24-25)
+
+  // The streamed writer's host batch (SetStreaming): keys and trimmed packed
+  // runs, empty keys and repeats, counted as the ordinary writer counts them.
+  // Fewer keys than a flush carries, and no Keys2Block / Final: nothing here
+  // reaches the device (a stream allocates nothing before its first append).
+  FilterBlockWriter plain(std::make_unique<BloomFilter>(10)), streamed(std::make_unique<BloomFilter>(10));
+  CHECK(plain.SetStreaming(false) == OK);
+  CHECK(streamed.SetStreaming(true) == OK && streamed.streaming());
+  std::string run;
+  std::vector<uint64_t> off{0};
+  for (int i = 0; i < 300; ++i) {
+    run += std::string((i / 3) % 7, (char)('a' + (i / 3) % 5)) + "123456789";  // 9 bytes to trim; runs of 3 equal keys
+    off.push_back(run.size());
+  }
+  for (FilterBlockWriter *fw : {&plain, &streamed}) {
+    for (const char *k : {"", "", "a", "a", "b", ""}) CHECK(fw->Update(k) == OK);
+    CHECK(fw->UpdateBatch(run.data(), off.data(), 300, 9) == OK);
+    CHECK(fw->Update(std::string((299 / 3) % 7, (char)('a' + (299 / 3) % 5))) == OK);  // equals the run's last key
+  }
+  CHECK(streamed.adjacent_duplicates() == plain.adjacent_duplicates() && plain.adjacent_duplicates() >= 200);
+  CHECK(streamed.SetStreaming(false) == BAD_RECORD);  // keys are pending
 }
 
 // The level index builder and its host lookup (level_index_core.hpp through

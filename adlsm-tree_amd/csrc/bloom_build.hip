@@ -648,6 +648,26 @@ struct SrcH {
   }
 };
 
+// The pairs of a streamed build (stream_build.hip): one per key, in key order,
+// linear over all the stream's filters -- filter d's keys start at
+// d.key_begin, so one store serves any number of filters (SrcH's chunk grid
+// serves the launch that hashed it only).
+struct SrcP {
+  const uint2 *h;
+  using Raw = uint2;
+  __device__ __forceinline__ Raw load(const FilterDesc &d, uint32_t, uint32_t first, uint32_t idx) const {
+    const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t *>(h + d.key_begin + first + idx));
+    return make_uint2(v.x, v.y);
+  }
+  __device__ static __forceinline__ void hash(const Raw &r, uint32_t &h1, uint32_t &h2) {
+    h1 = r.x;
+    h2 = r.y;
+  }
+};
+
+// (KeysPair, bloom_common.hpp, is the same store as a key view of the generic
+// pass A: any k, adjacent-duplicate skipping.)
+
 // Pass A for the hot path (16-byte keys, compile-time k).  Same output as
 // bloom_bin_kernel, with the chunk loop software-pipelined so VALU, LDS and
 // memory overlap inside one workgroup:
@@ -1537,8 +1557,9 @@ int launch_binned_dt(const Plan &p, Keys keys, uint8_t *d_bitmaps, void *ws, hip
     auto bin16 = [&](auto src, BuildArgs args, bool hashed) -> int {
       using S = decltype(src);
       a_queued = dyn_a;
-      a_kernel = hashed ? (p.claim ? "bin16 SrcH claim" : "bin16 SrcH dense")
-                        : (p.claim ? "bin16 Src16 claim" : "bin16 Src16 dense");
+      a_kernel = std::is_same<S, SrcP>::value ? (p.claim ? "bin16 SrcP claim" : "bin16 SrcP dense")
+                 : hashed                     ? (p.claim ? "bin16 SrcH claim" : "bin16 SrcH dense")
+                                              : (p.claim ? "bin16 Src16 claim" : "bin16 Src16 dense");
       if (p.claim) {
         args.claim = claim_used = 1;
         if (dyn_a)
@@ -1574,6 +1595,10 @@ int launch_binned_dt(const Plan &p, Keys keys, uint8_t *d_bitmaps, void *ws, hip
         av.dd_log2 = 0;
         rc = bin16(SrcH{hp, p.a.C}, av, true);
       }
+    }
+    if constexpr (std::is_same<Keys, KeysPair>::value) {
+      // a streamed build's pairs (the caller has set or cleared aa.dd_log2)
+      if (p.a.k == 6 && !p.a.dedup) rc = bin16(SrcP{keys.h}, aa, false);
     }
     if (rc < 0)
       rc = p.a.k == 6 ? go(adl_host::lds_limit<bloom_bin_kernel<B, 6, 6, Keys, DT>>, bloom_bin_kernel<B, 6, 6, Keys, DT>)
@@ -1617,13 +1642,11 @@ namespace {
 // (groups of at most 2^31 / k keys).
 uint64_t group_keys_max(int32_t bpk) { return (1ull << 31) / (uint64_t)adl_host::num_probes(bpk); }
 
-int build_groups(const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_stride,
-                 const uint64_t *key_begin, uint32_t num_filters, int32_t bpk, uint8_t *d_bitmaps,
-                 const uint64_t *bitmap_off, void *d_workspace, uint64_t workspace_bytes,
-                 hipStream_t st, uint32_t flags = 0) {
+// launch(plan, workspace): the key shape's launch_binned of one group.
+template <class Launch>
+int build_groups_with(const uint64_t *key_begin, uint32_t num_filters, int32_t bpk, const uint64_t *bitmap_off,
+                      void *d_workspace, uint64_t workspace_bytes, uint32_t flags, Launch launch) {
   if (flags & ~(uint32_t)ADL_BLOOM_SKIP_ADJACENT_DUPLICATES) return ADL_ERR_INVALID_ARG;
-  if (!d_keys && key_begin[num_filters] > key_begin[0]) return ADL_ERR_INVALID_ARG;
-  if (!d_offsets && key_stride == 0 && key_begin[num_filters] > key_begin[0]) return ADL_ERR_INVALID_ARG;
   if (bpk < 0) return ADL_ERR_INVALID_ARG;
   const uint64_t gmax = group_keys_max(bpk);
   std::vector<uint64_t> counts;
@@ -1651,23 +1674,50 @@ int build_groups(const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_
     }
     if (!d_workspace || workspace_bytes < p.ws_bytes) return ADL_ERR_WORKSPACE;
     void *ws = reinterpret_cast<void *>(adl_host::round_up(reinterpret_cast<uintptr_t>(d_workspace), 256));
-    if (d_offsets) {
-      KeysVar keys{d_keys, d_offsets};
-      // staging loads (pass A's windows and the hashing pass) read whole aligned
-      // 16-byte blocks: only of a 16-byte-aligned key buffer
-      if (reinterpret_cast<uintptr_t>(d_keys) % 16) p.a.stage_keys = 0;
-      rc = launch_binned(p, keys, d_bitmaps, ws, st);
-    } else if (key_stride == 16 && (reinterpret_cast<uintptr_t>(d_keys) % 16) == 0) {
-      rc = launch_binned(p, Keys16{reinterpret_cast<const uint4 *>(d_keys)}, d_bitmaps, ws, st);
-    } else {
-      rc = launch_binned(p, KeysStride{d_keys, key_stride}, d_bitmaps, ws, st);
-    }
+    rc = launch(p, ws);
     if (rc) return rc;
     g = e;
   }
   return ADL_OK;
 }
+
+int build_groups(const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_stride,
+                 const uint64_t *key_begin, uint32_t num_filters, int32_t bpk, uint8_t *d_bitmaps,
+                 const uint64_t *bitmap_off, void *d_workspace, uint64_t workspace_bytes,
+                 hipStream_t st, uint32_t flags = 0) {
+  if (flags & ~(uint32_t)ADL_BLOOM_SKIP_ADJACENT_DUPLICATES) return ADL_ERR_INVALID_ARG;
+  if (!d_keys && key_begin[num_filters] > key_begin[0]) return ADL_ERR_INVALID_ARG;
+  if (!d_offsets && key_stride == 0 && key_begin[num_filters] > key_begin[0]) return ADL_ERR_INVALID_ARG;
+  return build_groups_with(key_begin, num_filters, bpk, bitmap_off, d_workspace, workspace_bytes, flags,
+                           [&](Plan &p, void *ws) -> int {
+    if (d_offsets) {
+      KeysVar keys{d_keys, d_offsets};
+      // staging loads (pass A's windows and the hashing pass) read whole aligned
+      // 16-byte blocks: only of a 16-byte-aligned key buffer
+      if (reinterpret_cast<uintptr_t>(d_keys) % 16) p.a.stage_keys = 0;
+      return launch_binned(p, keys, d_bitmaps, ws, st);
+    }
+    if (key_stride == 16 && (reinterpret_cast<uintptr_t>(d_keys) % 16) == 0)
+      return launch_binned(p, Keys16{reinterpret_cast<const uint4 *>(d_keys)}, d_bitmaps, ws, st);
+    return launch_binned(p, KeysStride{d_keys, key_stride}, d_bitmaps, ws, st);
+  });
+}
 }  // namespace
+
+// Library-internal (stream_build.hip): the segmented build over a stream's
+// hash pairs, pair i at d_pairs[i]; the contracts of
+// adl_bloom_build_segmented_device_ex.  hash_dedup: pass A's repeated-pair
+// table where the plan and ADL_BLOOM_HASH_DEDUP allow it.
+int adl_host::adl_build_pairs_device(const void *d_pairs, const uint64_t *key_begin, uint32_t num_filters,
+                                     int32_t bpk, uint8_t *d_bitmaps, const uint64_t *bitmap_off, uint32_t flags,
+                                     bool hash_dedup, void *d_workspace, uint64_t workspace_bytes, hipStream_t st) {
+  if (!d_pairs && key_begin[num_filters] > key_begin[0]) return ADL_ERR_INVALID_ARG;
+  return build_groups_with(key_begin, num_filters, bpk, bitmap_off, d_workspace, workspace_bytes, flags,
+                           [&](Plan &p, void *ws) -> int {
+    if (!hash_dedup) p.a.dd_log2 = 0;
+    return launch_binned(p, KeysPair{static_cast<const uint2 *>(d_pairs)}, d_bitmaps, ws, st);
+  });
+}
 
 // ====================================================================== C-ABI
 extern "C" {

@@ -79,6 +79,25 @@ struct KeysVar {
   }
 };
 
+// The (h1, h2) pairs of a streamed build (stream_build.hip), pair i of key i,
+// as a key view of the generic pass A (bloom_build.hip: any k, adjacent-
+// duplicate skipping) and of the construction check (cache_build.hip).  Equal
+// pairs give equal positions, so skipping a key whose pair equals its
+// predecessor's leaves the bitmap as skipping an equal key does, and needs no
+// key bytes.
+struct KeysPair {
+  const uint2 *h;
+  __device__ __forceinline__ void hash(uint64_t i, uint32_t &h1, uint32_t &h2) const {
+    const uint2 v = h[i];
+    h1 = v.x;
+    h2 = v.y;
+  }
+  __device__ __forceinline__ bool same_as_prev(uint64_t i) const {
+    const uint2 a = h[i], b = h[i - 1];
+    return a.x == b.x && a.y == b.y;
+  }
+};
+
 // ---------------------------------------------------------------- nt access
 // Non-temporal 16-byte load/store (global_*_dwordx4 ... nt): streamed data that
 // should not displace what the next kernel re-reads from L2 / Infinity Cache.
@@ -217,6 +236,9 @@ struct Knobs {
   uint32_t claim = 3;             // ADL_BLOOM_CLAIM: 0 off, 1 wherever the share test passes, 2 forced, 3 auto
   uint32_t claim_cap = 0;         // ADL_BLOOM_CLAIM_CAP: claim region cap, percent of k*C (0: the LDS left)
   bool hash_dedup = true;         // ADL_BLOOM_HASH_DEDUP: pass A skips repeated hash pairs
+  // ADL_BLOOM_STREAM_HASH_DEDUP: the same table in a streamed finish (stream_build.hip): 0 off, 1 on,
+  // 2 (default) on when every key of the stream came as a 16-byte key, as the builds from keys have it
+  uint32_t stream_hash_dedup = 2;
   bool spin = true;               // ADL_BLOOM_SPIN: small cache probes watch their mapped answers
   bool probe_server = true;       // ADL_BLOOM_PROBE_SERVER: cache batches of <= 8 queries go to the server
   uint64_t server_idle_us = 2000;   // ADL_BLOOM_SERVER_IDLE_US
@@ -252,6 +274,7 @@ struct Knobs {
     claim = (uint32_t)u64("ADL_BLOOM_CLAIM", 3);
     claim_cap = (uint32_t)u64("ADL_BLOOM_CLAIM_CAP", 0);
     hash_dedup = u64("ADL_BLOOM_HASH_DEDUP", 1) != 0;
+    stream_hash_dedup = (uint32_t)u64("ADL_BLOOM_STREAM_HASH_DEDUP", 2);
     spin = u64("ADL_BLOOM_SPIN", 1) != 0;
     probe_server = u64("ADL_BLOOM_PROBE_SERVER", 1) != 0;
     server_idle_us = u64("ADL_BLOOM_SERVER_IDLE_US", 2000);
@@ -490,9 +513,10 @@ struct UploadRing {
     }
     for (uint8_t *h : retired) (void)hipHostFree(h);
   }
-  int upload(void *dst, const void *src, uint64_t bytes, hipStream_t st) {
+  // The next slot, free and at least `bytes` long: the caller fills *h and
+  // sends it with commit().  (A slot taken and not committed is simply reused.)
+  int begin(uint64_t bytes, uint8_t **h) {
     const int s = next;
-    next = (next + 1) % kSlots;
     if (!ev[s]) ADL_HIP_TRY(hipEventCreateWithFlags(&ev[s], hipEventDisableTiming));
     if (used[s]) ADL_HIP_TRY(hipEventSynchronize(ev[s]));
     used[s] = false;
@@ -504,11 +528,23 @@ struct UploadRing {
       ADL_HIP_TRY(hipHostMalloc((void **)&host[s], want, hipHostMallocDefault));
       cap[s] = want;
     }
-    memcpy(host[s], src, bytes);
+    *h = host[s];
+    return ADL_OK;
+  }
+  // The first `bytes` of the slot begin() gave go to dst in stream order.
+  int commit(void *dst, uint64_t bytes, hipStream_t st) {
+    const int s = next;
+    next = (next + 1) % kSlots;
     ADL_HIP_TRY(hipMemcpyAsync(dst, host[s], bytes, hipMemcpyHostToDevice, st));
     ADL_HIP_TRY(hipEventRecord(ev[s], st));
     used[s] = true;
     return ADL_OK;
+  }
+  int upload(void *dst, const void *src, uint64_t bytes, hipStream_t st) {
+    uint8_t *h = nullptr;
+    if (int rc = begin(bytes, &h)) return rc;
+    memcpy(h, src, bytes);
+    return commit(dst, bytes, st);
   }
 };
 
@@ -557,6 +593,31 @@ __attribute__((visibility("hidden"))) int adl_filter_block_build_into(
     const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_stride, const uint64_t *key_begin,
     uint32_t num_filters, int32_t bits_per_key, uint8_t *d_block, uint64_t block_bytes, uint32_t flags, bool in_place,
     void *d_workspace, uint64_t workspace_bytes, hipStream_t st);
+
+// Library-internal (bloom_build.hip): adl_bloom_build_segmented_device_ex over
+// the (h1, h2) pairs of a streamed build (stream_build.hip), pair i (a uint2)
+// at d_pairs[i], instead of keys.
+__attribute__((visibility("hidden"))) int adl_build_pairs_device(
+    const void *d_pairs, const uint64_t *key_begin, uint32_t num_filters, int32_t bits_per_key, uint8_t *d_bitmaps,
+    const uint64_t *bitmap_off, uint32_t flags, bool hash_dedup, void *d_workspace, uint64_t workspace_bytes,
+    hipStream_t st);
+
+// Library-internal (filter_block_device.hip): adl_filter_block_build_into over
+// a streamed build's pairs instead of keys.
+__attribute__((visibility("hidden"))) int adl_filter_block_build_into_pairs(
+    const void *d_pairs, bool hash_dedup, const uint64_t *key_begin, uint32_t num_filters, int32_t bits_per_key,
+    uint8_t *d_block, uint64_t block_bytes, uint32_t flags, bool in_place, void *d_workspace,
+    uint64_t workspace_bytes, hipStream_t st);
+
+// Library-internal (stream_build.hip), for a build that reads a stream's pair
+// store itself (cache_build.hip).  stream_acquire: `st` waits for the object's
+// appends (and earlier finishes); *d_pairs is the store, key_begin the bounds
+// of adl_bloom_stream_counts, *hash_dedup whether a finish would use pass A's
+// repeated-pair table.  stream_release: what was enqueued on `st` since counts
+// as a finish of the object.
+__attribute__((visibility("hidden"))) int stream_acquire(adl_bloom_stream *s, hipStream_t st, const void **d_pairs,
+                                                         std::vector<uint64_t> &key_begin, bool *hash_dedup);
+__attribute__((visibility("hidden"))) int stream_release(adl_bloom_stream *s, hipStream_t st);
 
 // adl_bloom_test_fault's armed sites (-1: off).  take() disarms and returns the
 // argument, so an armed fault fires once.

@@ -19,7 +19,10 @@
 //    bitmap region by one D2H, the trailer framed on the host.
 //  * publish(ticket, oid): once the file is written and its SHA-256 known,
 //    put's step 4 under the lock.  abandon(ticket) gives the range back.
-//  * bloom_verify_kernel: every build key probed again against the bitmap it
+//  * build_stream: the same with an adl_bloom_stream as the key source
+//    (stream_build.hip): nothing to upload, the filters are built from the
+//    stream's hash pairs.
+//  * bloom_verify_kernel: every build key (or pair) probed again against the bitmap it
 //    went into (the "probe what you inserted" check of storage engines; one
 //    streaming pass).  With ADL_BLOOM_CACHE_VERIFY a block with a missing key
 //    never goes resident.
@@ -256,22 +259,55 @@ int verify_launch(const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n, 
   });
 }
 
+// The same check from a streamed build's hash pairs (pair i of key i): the
+// keys are gone, and a pair is all the probe takes from a key.
+int verify_launch_pairs(const uint2 *d_pairs, uint64_t n, const uint64_t *d_key_begin, uint32_t nf,
+                        const uint8_t *d_bitmaps, const uint64_t *d_begin, int32_t bpk, uint64_t *d_result,
+                        hipStream_t st) {
+  ADL_HIP_TRY(hipMemsetAsync(d_result, 0, 8, st));
+  ADL_HIP_TRY(hipMemsetAsync(d_result + 1, 0xff, 8, st));
+  if (n == 0 || nf == 0) return ADL_OK;
+  const uint32_t k = (uint32_t)adl_host::num_probes(bpk);
+  size_t lds = 0;
+  if (nf <= kLdsFilters) lds = (size_t)nf * sizeof(ModLds) + (nf + 1 <= kLdsFilters ? ((size_t)nf + 1) * 8 : 0);
+  hipLaunchKernelGGL(bloom_verify_kernel<KeysPair>, dim3(adl_host::grid_for(n, kBlockP, 8)), dim3(kBlockP), lds, st,
+                     KeysPair{d_pairs}, n, k, d_key_begin, nf, d_bitmaps, d_begin, (const uint64_t *)nullptr,
+                     reinterpret_cast<unsigned long long *>(d_result));
+  ADL_HIP_TRY(hipGetLastError());
+  return ADL_OK;
+}
+
+// What a build's filters are built from: device keys, or (d_pairs set) a
+// streamed build's hash pairs.
+struct BuildSource {
+  const uint8_t *d_keys = nullptr;
+  const uint64_t *d_offsets = nullptr;
+  uint32_t key_stride = 0;
+  bool from_pairs = false;
+  const uint2 *d_pairs = nullptr;  // (may be NULL when the stream holds no key)
+  bool pair_dedup = false;         // pairs: pass A's repeated-pair table
+};
+
 // Everything a build enqueues on `st`: the filters into the arena range of
 // `mine`, the test fault, the verify pass (result to d_result) and the D2H of
 // the bitmap region into h_dst (pinned, or NULL).  key_begin: HOST, relative
 // to d_keys / d_offsets.  d_ws: 256-byte aligned.
-int enqueue_build(Cache *c, Cache::Iter mine, const BlockPlan &P, const uint8_t *d_keys, const uint64_t *d_offsets,
-                  uint32_t key_stride, const uint64_t *key_begin, uint32_t nf, int32_t bpk, uint32_t flags,
-                  uint8_t *d_ws, uint64_t ws_bytes, uint64_t **d_result, uint8_t *h_dst, hipStream_t st) {
+int enqueue_build(Cache *c, Cache::Iter mine, const BlockPlan &P, const BuildSource &src, const uint64_t *key_begin,
+                  uint32_t nf, int32_t bpk, uint32_t flags, uint8_t *d_ws, uint64_t ws_bytes, uint64_t **d_result,
+                  uint8_t *h_dst, hipStream_t st) {
   uint8_t *range = c->arena + mine->base;
   uint64_t *d_aux = reinterpret_cast<uint64_t *>(d_ws);
   *d_result = reinterpret_cast<uint64_t *>(d_ws + aux_bytes(nf));
   uint8_t *bws = d_ws + aux_bytes(nf) + 256;
   if (ws_bytes < aux_bytes(nf) + 256) return ADL_ERR_WORKSPACE;
-  if (int rc = adl_host::adl_filter_block_build_into(d_keys, d_offsets, key_stride, key_begin, nf, bpk, range,
-                                                     mine->size, flags & ADL_BLOOM_SKIP_ADJACENT_DUPLICATES, true,
-                                                     bws, ws_bytes - aux_bytes(nf) - 256, st))
-    return rc;
+  const int brc = src.from_pairs
+                      ? adl_host::adl_filter_block_build_into_pairs(src.d_pairs, src.pair_dedup, key_begin, nf, bpk, range,
+                                                                    mine->size, flags & ADL_BLOOM_SKIP_ADJACENT_DUPLICATES,
+                                                                    true, bws, ws_bytes - aux_bytes(nf) - 256, st)
+                      : adl_host::adl_filter_block_build_into(src.d_keys, src.d_offsets, src.key_stride, key_begin, nf, bpk,
+                                                              range, mine->size, flags & ADL_BLOOM_SKIP_ADJACENT_DUPLICATES,
+                                                              true, bws, ws_bytes - aux_bytes(nf) - 256, st);
+  if (brc) return brc;
   if (adl_host::g_test_faults.take(ADL_TEST_FAULT_CACHE_BUILD_CORRUPT) >= 0 && P.off[1] > P.off[0]) {
     hipLaunchKernelGGL(cache_corrupt_kernel, dim3(1), dim3(256), 0, st, range, P.off[1]);
     ADL_HIP_TRY(hipGetLastError());
@@ -280,9 +316,11 @@ int enqueue_build(Cache *c, Cache::Iter mine, const BlockPlan &P, const uint8_t 
     std::vector<uint64_t> aux(key_begin, key_begin + nf + 1);
     aux.insert(aux.end(), P.off.begin(), P.off.end());
     if (int rc = adl_host::t_upload.upload(d_aux, aux.data(), aux.size() * 8, st)) return rc;
-    if (int rc = verify_launch(d_keys, d_offsets, key_begin[nf], key_stride, d_aux, nf, range, d_aux + nf + 1,
-                               nullptr, bpk, *d_result, st))
-      return rc;
+    const int vrc = src.from_pairs
+                        ? verify_launch_pairs(src.d_pairs, key_begin[nf], d_aux, nf, range, d_aux + nf + 1, bpk, *d_result, st)
+                        : verify_launch(src.d_keys, src.d_offsets, key_begin[nf], src.key_stride, d_aux, nf, range,
+                                        d_aux + nf + 1, nullptr, bpk, *d_result, st);
+    if (vrc) return vrc;
   }
   if (h_dst && P.region()) ADL_HIP_TRY(hipMemcpyAsync(h_dst, range, P.region(), hipMemcpyDeviceToHost, st));
   return ADL_OK;
@@ -368,8 +406,11 @@ int adl_bloom_filter_cache_build(adl_bloom_filter_cache *c, const uint8_t *h_key
         const uint8_t *d_keys = h_offsets ? d_in - b0 : d_in;
         const uint64_t *d_offs = off_bytes ? reinterpret_cast<const uint64_t *>(d_in + kb_al) : nullptr;
         // (a block of empty var-len filters has no offsets to upload: any stride serves)
-        if (int r = enqueue_build(c, t->it, P, d_keys, d_offs, d_offs ? 0 : (key_stride ? key_stride : 16),
-                                  local.data(), nf, bits_per_key, flags, d_ws, ws_bytes, &d_result,
+        BuildSource src;
+        src.d_keys = d_keys;
+        src.d_offsets = d_offs;
+        src.key_stride = d_offs ? 0 : (key_stride ? key_stride : 16);
+        if (int r = enqueue_build(c, t->it, P, src, local.data(), nf, bits_per_key, flags, d_ws, ws_bytes, &d_result,
                                   pin_out ? h_block : sg.host + ho_out, st))
           return r;
         if (flags & ADL_BLOOM_CACHE_VERIFY)
@@ -451,7 +492,11 @@ int adl_bloom_filter_cache_build_device(adl_bloom_filter_cache *c, const uint8_t
     if (rc == ADL_OK && nf) {
       rc = [&]() -> int {
         uint64_t *d_result = nullptr;
-        if (int r = enqueue_build(c, t->it, P, d_keys, d_offsets, key_stride, key_begin, nf, bits_per_key, flags,
+        BuildSource src;
+        src.d_keys = d_keys;
+        src.d_offsets = d_offsets;
+        src.key_stride = key_stride;
+        if (int r = enqueue_build(c, t->it, P, src, key_begin, nf, bits_per_key, flags,
                                   static_cast<uint8_t *>(d_workspace), workspace_bytes, &d_result, h_block, st))
           return r;
         if (verify)
@@ -475,6 +520,83 @@ int adl_bloom_filter_cache_build_device(adl_bloom_filter_cache *c, const uint8_t
       return rc;
     }
     if (h_block) frame_trailer(h_block, P, nf, bits_per_key);  // (behind the bytes the D2H writes)
+    *ticket = t;
+    return ADL_OK;
+  } catch (...) {
+    return ADL_ERR_OUT_OF_MEMORY;
+  }
+}
+
+// The write-through build with a stream as its key source: as
+// adl_bloom_filter_cache_build, with nothing to upload -- the filters are
+// built from the stream's pairs into the reserved range, and with
+// ADL_BLOOM_CACHE_VERIFY every pair is probed again.
+int adl_bloom_filter_cache_build_stream(adl_bloom_filter_cache *c, adl_bloom_stream *s, int32_t bits_per_key,
+                                        uint32_t flags, uint8_t *h_block, uint64_t block_capacity,
+                                        uint64_t *block_bytes, adl_bloom_cache_ticket **ticket, void *stream) {
+  if (flags & ~kKnownFlags) return ADL_ERR_INVALID_ARG;
+  if (!c || !s || !h_block || !block_bytes || !ticket || bits_per_key < 0) return ADL_ERR_INVALID_ARG;
+  *ticket = nullptr;
+  *block_bytes = 0;
+  try {
+    uint32_t nf = 0;
+    if (int rc = adl_bloom_stream_counts(s, &nf, nullptr, 0)) return rc;
+    std::vector<uint64_t> kb((size_t)nf + 1, 0);
+    if (int rc = adl_bloom_stream_counts(s, &nf, kb.data(), nf + 1)) return rc;
+    BlockPlan P;
+    if (int rc = plan_block(kb.data(), nf, bits_per_key, P)) return rc;
+    *block_bytes = P.block_bytes;
+    if (block_capacity < P.block_bytes) return ADL_ERR_INVALID_ARG;
+    const uint64_t ws_bytes = adl_bloom_filter_cache_build_workspace_bytes(kb.data(), nf, bits_per_key);
+    if (!ws_bytes) return ADL_ERR_TOO_LARGE;
+    auto *t = new adl_bloom_cache_ticket;
+    const uint64_t size = adl_host::round_up(std::max(P.block_bytes, P.region() + 1), kAlign);
+    if (int rc = reserve_range(c, size, std::vector<uint64_t>(P.off), (uint8_t)adl_host::num_probes(bits_per_key),
+                               t->it)) {
+      delete t;
+      return rc;
+    }
+    hipStream_t st = adl_host::sync_stream(stream);
+    const bool pin_out = adl_host::is_pinned(h_block);
+    // pinned host staging: [verify result][bitmap region]; device: the workspace
+    const uint64_t ho_out = 256, hbytes = ho_out + (pin_out ? 0 : adl_host::round_up(P.region(), 256));
+    adl_host::Staging &sg = adl_host::t_stage;
+    int rc = sg.reserve(hbytes, ws_bytes);
+    if (rc == ADL_OK && nf) {
+      rc = [&]() -> int {
+        BuildSource src;
+        src.from_pairs = true;
+        const void *pairs = nullptr;
+        std::vector<uint64_t> kb2;
+        if (int r = adl_host::stream_acquire(s, st, &pairs, kb2, &src.pair_dedup)) return r;
+        src.d_pairs = static_cast<const uint2 *>(pairs);
+        uint64_t *d_result = nullptr;
+        if (int r = enqueue_build(c, t->it, P, src, kb.data(), nf, bits_per_key, flags, sg.dev, ws_bytes, &d_result,
+                                  pin_out ? h_block : sg.host + ho_out, st))
+          return r;
+        if (flags & ADL_BLOOM_CACHE_VERIFY)
+          ADL_HIP_TRY(hipMemcpyAsync(sg.host, d_result, 16, hipMemcpyDeviceToHost, st));
+        return adl_host::stream_release(s, st);
+      }();
+      // every exit waits for what was enqueued (the block, the arena range, the stream's pairs)
+      if (hipStreamSynchronize(st) != hipSuccess && rc == ADL_OK) rc = ADL_ERR_DEVICE;
+      if (rc != ADL_OK) (void)hipGetLastError();
+    }
+    if (rc == ADL_OK && nf && (flags & ADL_BLOOM_CACHE_VERIFY)) {
+      uint64_t res[2];
+      memcpy(res, sg.host, 16);
+      if (res[0]) {
+        report_missing(res[0], res[1]);
+        rc = ADL_FILTER_BLOCK_ERROR;
+      }
+    }
+    if (rc != ADL_OK) {
+      release_range(c, t->it);
+      delete t;
+      return rc;
+    }
+    if (!pin_out && P.region()) memcpy(h_block, sg.host + ho_out, P.region());
+    frame_trailer(h_block, P, nf, bits_per_key);
     *ticket = t;
     return ADL_OK;
   } catch (...) {

@@ -184,10 +184,52 @@ void BloomFilter::FilterInfo(string &info) {
 // ------------------------------------------------------------- FilterBlockWriter
 
 FilterBlockWriter::FilterBlockWriter(unique_ptr<FilterAlgorithm> &&method)
-    : method_(std::move(method)) {}
+    : method_(std::move(method)) {
+  bloom_ = dynamic_cast<BloomFilter *>(method_.get());
+  if (const char *e = getenv("ADL_BLOOM_STREAM_BATCH_KEYS"); e && *e)
+    batch_limit_ = std::max<size_t>(1, strtoull(e, nullptr, 10));
+  if (const char *e = getenv("ADL_BLOOM_STREAM_BUILD"); e && *e && strtoull(e, nullptr, 10) != 0) SetStreaming(true);
+}
+
+void FilterBlockWriter::StreamDeleter::operator()(adl_bloom_stream *s) const { adl_bloom_stream_destroy(s); }
+
+RC FilterBlockWriter::SetStreaming(bool on) {
+  if (keys_.size() || bounds_.size() > 1 || stream_keys_ || stream_cut_) return BAD_RECORD;
+  streaming_ = on;
+  if (on && bloom_ && !stream_) {
+    adl_bloom_stream *s = nullptr;
+    if (int st = adl_bloom_stream_create(std::min<size_t>(batch_limit_, 65536), &s); st != ADL_OK) {
+      streaming_ = false;
+      return FromStatus(st);
+    }
+    stream_.reset(s);
+  }
+  return OK;
+}
+
+/* The host batch goes to the device: uploaded and hashed in stream order, not
+ * waited for.  A failure is kept for Final (Update's callers drop its RC, as
+ * the reference's do). */
+RC FilterBlockWriter::FlushBatch() {
+  if (batch_.empty()) return OK;
+  last_key_.assign(batch_.key(batch_.size() - 1));
+  have_last_ = true;
+  const int st = adl_bloom_stream_append(stream_.get(), reinterpret_cast<const uint8_t *>(batch_.bytes().data()),
+                                         batch_.offsets().data(), batch_.size(), 0, nullptr);
+  batch_.Clear();
+  if (st != ADL_OK && stream_status_ == ADL_OK) stream_status_ = st;
+  return FromStatus(st);
+}
 
 /* src/filter_block.cpp:72-75 */
 RC FilterBlockWriter::Update(string_view key) {
+  if (streaming()) {
+    if (batch_.empty() ? (have_last_ && key == string_view(last_key_)) : key == batch_.key(batch_.size() - 1)) ++dups_;
+    batch_.Add(key);
+    ++stream_keys_;
+    if (batch_.size() >= batch_limit_) return FlushBatch();
+    return OK;
+  }
   const size_t from = keys_.size();
   keys_.Add(key);
   CountDuplicates(from);
@@ -195,6 +237,17 @@ RC FilterBlockWriter::Update(string_view key) {
 }
 
 RC FilterBlockWriter::UpdateBatch(const char *base, const uint64_t *off, size_t n, size_t trim) {
+  if (streaming()) {
+    const size_t from = batch_.size();
+    batch_.AddTrimmed(base, off, n, trim);
+    for (size_t i = from; i < batch_.size(); ++i) {
+      if (i > 0) dups_ += batch_.key(i) == batch_.key(i - 1);
+      else if (have_last_) dups_ += batch_.key(i) == string_view(last_key_);
+    }
+    stream_keys_ += n;
+    if (batch_.size() >= batch_limit_) return FlushBatch();
+    return OK;
+  }
   const size_t from = keys_.size();
   keys_.AddTrimmed(base, off, n, trim);
   CountDuplicates(from);
@@ -211,7 +264,67 @@ void FilterBlockWriter::CountDuplicates(size_t from) {
 /* src/filter_block.cpp:104-109 -- closes the current filter; its bitmap is
  * built with all the others in Final(). */
 RC FilterBlockWriter::Keys2Block() {
+  if (streaming()) {
+    FlushBatch();
+    have_last_ = false;  // the next filter's first key has no predecessor
+    stream_cut_ = true;
+    return FromStatus(adl_bloom_stream_cut(stream_.get()));
+  }
   bounds_.push_back(keys_.size());
+  return OK;
+}
+
+/* [int32 offsets][int32 offsets_start][int32 num_filters][info][int32 info_len]
+ * behind the bitmaps in buffer_, which moves out into `result`. */
+void FilterBlockWriter::Frame(const vector<uint64_t> &offsets, string &result) {
+  const int offsets_start = (int)buffer_.size();
+  for (uint64_t off : offsets) Append32(buffer_, (int)off);
+  Append32(buffer_, offsets_start);
+  Append32(buffer_, (int)offsets.size());
+  string info;
+  method_->FilterInfo(info);
+  if (!info.empty()) {
+    buffer_.append(info);
+    Append32(buffer_, (int)info.size());
+  }
+  result = std::move(buffer_);
+  buffer_.clear();
+}
+
+/* Final of the streamed writer: the tail batch, then every filter from the
+ * stream's hash pairs straight into the block (no key is uploaded or hashed
+ * here), and the trailer on the host as ever. */
+RC FilterBlockWriter::FinalStreamed(string &result) {
+  FlushBatch();
+  adl_bloom_stream *s = stream_.get();
+  uint32_t nf = 0;
+  int st = stream_status_ != ADL_OK ? stream_status_ : adl_bloom_stream_counts(s, &nf, nullptr, 0);
+  vector<uint64_t> kb(nf + 1, 0), offsets(nf, 0);
+  if (st == ADL_OK) st = adl_bloom_stream_counts(s, &nf, kb.data(), nf + 1);
+  const bool skip = dups_ * kSkipDuplicatesDen >= stream_keys_ * kSkipDuplicatesNum && dups_ > 0;
+  uint64_t total = 0;
+  for (uint32_t f = 0; f < nf && st == ADL_OK; ++f) {
+    const uint64_t bytes = adl_bloom_bitmap_bytes(kb[f + 1] - kb[f], bloom_->bits_per_key());
+    if (bytes == 0) st = ADL_ERR_TOO_LARGE;
+    offsets[f] = buffer_.size() + total;
+    total += bytes;
+  }
+  if (st == ADL_OK && nf) {
+    buffer_.resize(buffer_.size() + total);
+    st = adl_bloom_stream_finish(s, bloom_->bits_per_key(), skip ? ADL_BLOOM_SKIP_ADJACENT_DUPLICATES : 0u,
+                                 reinterpret_cast<uint8_t *>(&buffer_[0]), offsets.data(), nullptr);
+  }
+  adl_bloom_stream_reset(s);
+  have_last_ = false;
+  stream_keys_ = 0;
+  stream_cut_ = false;
+  stream_status_ = ADL_OK;
+  dups_ = 0;
+  if (st != ADL_OK) {
+    buffer_.clear();
+    return FromStatus(st);
+  }
+  Frame(offsets, result);
   return OK;
 }
 
@@ -219,6 +332,7 @@ RC FilterBlockWriter::Keys2Block() {
  * [int32 num_filters][info]["int32 info_len"], moved out into `result`.
  * Returns the first Keys2Block failure (the reference cannot fail here). */
 RC FilterBlockWriter::Final(string &result) {
+  if (streaming()) return FinalStreamed(result);
   if (keys_.size() > bounds_.back()) Keys2Block();
   vector<uint64_t> offsets;
   // Skipping duplicates runs the generic pass A (keys in their order), which
@@ -232,18 +346,7 @@ RC FilterBlockWriter::Final(string &result) {
     buffer_.clear();
     return rc;
   }
-  const int offsets_start = (int)buffer_.size();
-  for (uint64_t off : offsets) Append32(buffer_, (int)off);
-  Append32(buffer_, offsets_start);
-  Append32(buffer_, (int)offsets.size());
-  string info;
-  method_->FilterInfo(info);
-  if (!info.empty()) {
-    buffer_.append(info);
-    Append32(buffer_, (int)info.size());
-  }
-  result = std::move(buffer_);
-  buffer_.clear();
+  Frame(offsets, result);
   return OK;
 }
 
@@ -255,6 +358,29 @@ RC FilterBlockWriter::Final(string &result, FilterCache &cache, FilterCacheTicke
   t = FilterCacheTicket();
   auto *bloom = dynamic_cast<BloomFilter *>(method_.get());
   if (!bloom || cache.status() != OK) return Final(result);
+  if (streaming()) {
+    // the cache build starts from the stream's pairs; a failure that is not a
+    // filter error falls back to the ordinary streamed build, from the same
+    // stream (the keys are gone)
+    FlushBatch();
+    if (stream_status_ != ADL_OK) return FinalStreamed(result);  // (reports the failed append)
+    const bool skip = dups_ * kSkipDuplicatesDen >= stream_keys_ * kSkipDuplicatesNum && dups_ > 0;
+    const uint32_t flags = (skip ? ADL_BLOOM_SKIP_ADJACENT_DUPLICATES : 0u) | (verify ? ADL_BLOOM_CACHE_VERIFY : 0u);
+    const RC rc = cache.BuildStream(stream_.get(), bloom->bits_per_key(), flags, buffer_, t);
+    if (rc != OK && rc != FILTER_BLOCK_ERROR) return FinalStreamed(result);
+    adl_bloom_stream_reset(stream_.get());
+    have_last_ = false;
+    stream_keys_ = 0;
+    stream_cut_ = false;
+    dups_ = 0;
+    if (rc != OK) {
+      buffer_.clear();
+      return rc;
+    }
+    result = std::move(buffer_);
+    buffer_.clear();
+    return OK;
+  }
   if (keys_.size() > bounds_.back()) Keys2Block();
   const bool skip = dups_ * kSkipDuplicatesDen >= keys_.size() * kSkipDuplicatesNum && dups_ > 0;
   const uint32_t flags = (skip ? ADL_BLOOM_SKIP_ADJACENT_DUPLICATES : 0u) | (verify ? ADL_BLOOM_CACHE_VERIFY : 0u);
@@ -277,6 +403,30 @@ RC FilterBlockWriter::Final(string &result, FilterCache &cache, FilterCacheTicke
 void FilterCacheTicket::Reset() {
   if (t_) adl_bloom_filter_cache_abandon(cache_, t_);
   t_ = nullptr;
+}
+
+RC FilterCache::BuildStream(adl_bloom_stream *stream, int bits_per_key, uint32_t flags, string &block, Ticket &t) {
+  t = Ticket();
+  if (!h_) return status_;
+  uint32_t nf = 0;
+  if (int st = adl_bloom_stream_counts(stream, &nf, nullptr, 0); st != ADL_OK) return FromStatus(st);
+  vector<uint64_t> kb(nf + 1, 0);
+  if (int st = adl_bloom_stream_counts(stream, &nf, kb.data(), nf + 1); st != ADL_OK) return FromStatus(st);
+  const uint64_t bytes = adl_bloom_filter_block_bytes(kb.data(), nf, bits_per_key);
+  if (bytes == 0) return OUT_OF_RANGE;
+  block.resize(bytes);
+  adl_bloom_cache_ticket *raw = nullptr;
+  uint64_t got = 0;
+  const int st = adl_bloom_filter_cache_build_stream(h_, stream, bits_per_key, flags,
+                                                     reinterpret_cast<uint8_t *>(&block[0]), bytes, &got, &raw, nullptr);
+  if (st != ADL_OK) {
+    block.clear();
+    return FromStatus(st);
+  }
+  block.resize(got);
+  t.cache_ = h_;
+  t.t_ = raw;
+  return OK;
 }
 
 RC FilterCache::Build(const KeyArena &keys, const vector<uint64_t> &key_begin, int bits_per_key, uint32_t flags,

@@ -30,6 +30,7 @@
 struct adl_bloom_filter_set;
 struct adl_bloom_filter_cache;
 struct adl_bloom_cache_ticket;
+struct adl_bloom_stream;
 
 namespace adl {
 
@@ -173,9 +174,40 @@ class FilterBlockWriter {
   RC Keys2Block();
   /* keys added since the last Final that equal the previous key of their filter */
   uint64_t adjacent_duplicates() const { return dups_; }
+  /* Streamed build (adl_bloom_stream): Update / UpdateBatch collect keys in a
+   * small host batch that is uploaded and hashed on the device whenever it
+   * reaches ADL_BLOOM_STREAM_BATCH_KEYS keys (default 1048576); the writer keeps
+   * no other copy of the keys, only the last one of the open filter (for
+   * adjacent_duplicates).  Keys2Block flushes and cuts; Final flushes the
+   * tail, builds every filter from the stored hash pairs and frames the block
+   * on the host.  Block bytes, RCs and adjacent_duplicates() are those of the
+   * ordinary writer.  Only valid while no key or filter is pending
+   * (BAD_RECORD otherwise); ignored when the algorithm is not the BloomFilter.
+   * Final through a FilterCache goes through FilterCache::BuildStream (the
+   * block built from the stream straight into the arena, verify from the
+   * pairs); its fallback to the ordinary build finishes from the same stream.
+   * The default is off, or on with ADL_BLOOM_STREAM_BUILD=1. */
+  RC SetStreaming(bool on);
+  bool streaming() const { return streaming_ && bloom_; }
 
  private:
+  struct StreamDeleter {
+    void operator()(adl_bloom_stream *s) const;
+  };
   void CountDuplicates(size_t from);
+  RC FlushBatch();
+  RC FinalStreamed(string &result);
+  void Frame(const vector<uint64_t> &offsets, string &result);
+  bool streaming_ = false;
+  BloomFilter *bloom_ = nullptr;  /* method_ when it is the BloomFilter */
+  unique_ptr<adl_bloom_stream, StreamDeleter> stream_;
+  KeyArena batch_;               /* streaming: keys of the open filter not yet appended */
+  string last_key_;              /* streaming: the last key appended to the open filter */
+  bool have_last_ = false;
+  uint64_t stream_keys_ = 0;     /* streaming: keys since the last Final */
+  bool stream_cut_ = false;      /* streaming: a filter was closed since the last Final */
+  size_t batch_limit_ = 1048576;  /* DESIGN.md section 5, streamed build */
+  int stream_status_ = 0;        /* streaming: the first failed append's status, returned by Final */
   KeyArena keys_;              /* keys of every filter not yet built */
   vector<uint64_t> bounds_{0}; /* filter f = keys_ [bounds_[f], bounds_[f+1]) */
   uint64_t dups_ = 0;          /* adjacent duplicates among keys_ (CountDuplicates) */
@@ -212,6 +244,9 @@ class FilterCache {
   using Ticket = FilterCacheTicket;
   RC Build(const KeyArena &keys, const vector<uint64_t> &key_begin, int bits_per_key, uint32_t flags, string &block,
            Ticket &t);
+  /* The same with a stream (adl_bloom_stream) as the key source
+   * (adl_bloom_filter_cache_build_stream): the streamed writer's cache path. */
+  RC BuildStream(adl_bloom_stream *stream, int bits_per_key, uint32_t flags, string &block, Ticket &t);
   RC Publish(Ticket &t, string_view oid);
   RC Abandon(Ticket &t);
   /* arena bytes in use (blocks, tickets' ranges) and cached tables */

@@ -187,12 +187,14 @@ int adl_bloom_filter_block_build_device(const uint8_t *d_keys, const uint64_t *d
 // on the device (the caller frames it on the host).  The build writes the
 // bitmap's adl_bloom_bitmap_alloc_bytes there, pad bytes included: d_block
 // must have room for them.
-int adl_host::adl_filter_block_build_into(const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_stride,
-                                          const uint64_t *key_begin, uint32_t num_filters, int32_t bits_per_key,
-                                          uint8_t *d_block, uint64_t block_bytes, uint32_t flags, bool in_place,
-                                          void *d_workspace, uint64_t workspace_bytes, hipStream_t st) {
+namespace {
+// build(nf, bitmaps, bitmap_off, workspace, workspace_bytes): the segmented
+// build of the block's filters from wherever their keys are.
+template <class Build>
+int block_build_into(Build build, const uint64_t *key_begin, uint32_t num_filters, int32_t bits_per_key,
+                     uint8_t *d_block, uint64_t block_bytes, bool in_place, void *d_workspace,
+                     uint64_t workspace_bytes, hipStream_t st) {
   try {
-    void *stream = st;
     Layout L;
     if (int rc = layout(key_begin, num_filters, bits_per_key, L)) return rc;
     if (!d_block || reinterpret_cast<uintptr_t>(d_block) % 16 || block_bytes < L.block_bytes)
@@ -201,16 +203,13 @@ int adl_host::adl_filter_block_build_into(const uint8_t *d_keys, const uint64_t 
     if (!d_workspace || workspace_bytes < need) return ADL_ERR_WORKSPACE;
     if (in_place && num_filters == 1) {
       if (block_bytes < adl_host::round_up(L.bytes[0], 16)) return ADL_ERR_INVALID_ARG;
-      return adl_bloom_build_segmented_device_ex(d_keys, d_offsets, key_stride, key_begin, 1, bits_per_key, d_block,
-                                                 L.dst.data(), flags, d_workspace, workspace_bytes, stream);
+      return build(1u, d_block, L.dst.data(), d_workspace, workspace_bytes);
     }
     uint8_t *staging = reinterpret_cast<uint8_t *>(adl_host::round_up(reinterpret_cast<uintptr_t>(d_workspace), 256));
     uint8_t *bws = staging + L.staging_bytes;
     const uint64_t bws_bytes = workspace_bytes - (uint64_t)(bws - reinterpret_cast<uint8_t *>(d_workspace));
     if (num_filters) {
-      const int rc = adl_bloom_build_segmented_device_ex(d_keys, d_offsets, key_stride, key_begin, num_filters,
-                                                         bits_per_key, staging, L.src.data(), flags, bws, bws_bytes,
-                                                         stream);
+      const int rc = build(num_filters, staging, L.src.data(), (void *)bws, bws_bytes);
       if (rc) return rc;
     }
     const uint32_t cus = adl_host::device_cus();
@@ -244,4 +243,32 @@ int adl_host::adl_filter_block_build_into(const uint8_t *d_keys, const uint64_t 
   } catch (...) {
     return ADL_ERR_DEVICE;
   }
+}
+}  // namespace
+
+int adl_host::adl_filter_block_build_into(const uint8_t *d_keys, const uint64_t *d_offsets, uint32_t key_stride,
+                                          const uint64_t *key_begin, uint32_t num_filters, int32_t bits_per_key,
+                                          uint8_t *d_block, uint64_t block_bytes, uint32_t flags, bool in_place,
+                                          void *d_workspace, uint64_t workspace_bytes, hipStream_t st) {
+  return block_build_into(
+      [&](uint32_t nf, uint8_t *out, const uint64_t *off, void *ws, uint64_t ws_bytes) -> int {
+        return adl_bloom_build_segmented_device_ex(d_keys, d_offsets, key_stride, key_begin, nf, bits_per_key, out, off,
+                                                   flags, ws, ws_bytes, (void *)st);
+      },
+      key_begin, num_filters, bits_per_key, d_block, block_bytes, in_place, d_workspace, workspace_bytes, st);
+}
+
+// The same block from a streamed build's hash pairs (stream_build.hip), pair i
+// of key i at d_pairs[i]: the write-through build of a streamed writer.
+int adl_host::adl_filter_block_build_into_pairs(const void *d_pairs, bool hash_dedup, const uint64_t *key_begin,
+                                                uint32_t num_filters, int32_t bits_per_key, uint8_t *d_block,
+                                                uint64_t block_bytes, uint32_t flags, bool in_place, void *d_workspace,
+                                                uint64_t workspace_bytes, hipStream_t st) {
+  return block_build_into(
+      [&](uint32_t nf, uint8_t *out, const uint64_t *off, void *ws, uint64_t ws_bytes) -> int {
+        if (!out || reinterpret_cast<uintptr_t>(out) % 16) return ADL_ERR_INVALID_ARG;
+        return adl_host::adl_build_pairs_device(d_pairs, key_begin, nf, bits_per_key, out, off, flags, hash_dedup, ws,
+                                                ws_bytes, st);
+      },
+      key_begin, num_filters, bits_per_key, d_block, block_bytes, in_place, d_workspace, workspace_bytes, st);
 }

@@ -1,7 +1,8 @@
 // adlsm-tree_amd/csrc/hash_run.hpp -- both murmur hashes of a run of keys that
 // are not aligned 16-byte keys, hashed from LDS in length order.  The one run
-// hasher of the build (hash_var_kernel, bloom_build.hip) and of the binned
-// probe (pb_hash_kernel, probe_binned.hip).
+// hasher of the build (hash_var_kernel, bloom_build.hip), of the binned probe
+// (pb_hash_kernel, probe_binned.hip) and of a streamed build's appends
+// (stream_hash_run_kernel, stream_build.hip).
 //
 // A wave hashes 64 keys in lockstep, so it costs as much as its longest key;
 // keys sorted by exact length within a run of S keys give waves of nearly
@@ -77,6 +78,17 @@ struct ReadExactBytes {
 struct RunNoHook {
   __device__ __forceinline__ void operator()(int) const {}
   __device__ __forceinline__ static constexpr bool no_hash() { return false; }
+};
+
+// Output at the key's own index in the run: out[ix] = (h1, h2).  The binned
+// probe's query pairs (pb_hash_kernel) and a streamed build's pair store
+// (stream_hash_run_kernel, stream_build.hip) are both in key order.
+struct PairsByIndex {
+  uint2 *out;
+  static constexpr bool kByIndex = true;
+  __device__ __forceinline__ void operator()(uint32_t, uint32_t ix, uint32_t h1, uint32_t h2) const {
+    out[ix] = make_uint2(h1, h2);
+  }
 };
 
 // Keys [first, first + cnt) of `keys` (anything with `keys` and off(i)),

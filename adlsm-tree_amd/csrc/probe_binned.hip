@@ -416,13 +416,7 @@ __device__ __forceinline__ void load_runs(const uint32_t *cnt, const uint32_t *s
 constexpr int kPhBlk = 256;
 constexpr uint32_t kPhRun = 512;  // queries per run (the build's measured shape)
 
-struct PhOut {  // at the query's own index
-  uint2 *qh;
-  static constexpr bool kByIndex = true;
-  __device__ __forceinline__ void operator()(uint32_t, uint32_t ix, uint32_t h1, uint32_t h2) const {
-    qh[ix] = make_uint2(h1, h2);
-  }
-};
+using PhOut = PairsByIndex;  // at the query's own index
 
 template <uint32_t S, class Keys>
 __global__ __launch_bounds__(kPhBlk) void pb_hash_kernel(Keys keys, uint64_t n, uint2 *__restrict__ qh) {

@@ -176,6 +176,10 @@ class SSTableWriter {
     cache_ = cache;
     verify_ = verify;
   }
+  /* The filter block built from hash pairs kept on the device while the table
+   * fills (FilterBlockWriter::SetStreaming): valid before the first Add; the
+   * file and its oid are unchanged. */
+  RC SetStreamingFilter(bool on) { return filter_block_.SetStreaming(on); }
   int GetFileSize() const { return offset_; }
   /* filter keys added so far that equal their predecessor (user keys of
    * consecutive versions); Final skips them on the device when frequent */

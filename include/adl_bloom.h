@@ -152,6 +152,89 @@ int adl_bloom_build_segmented_ex(const uint8_t *h_keys, const uint64_t *h_offset
                                  const uint64_t *key_begin, uint32_t num_filters, int32_t bits_per_key,
                                  uint8_t *h_bitmaps, const uint64_t *h_bitmap_off, uint32_t flags, void *stream);
 
+/* --------------------------------------------------------- streamed build */
+
+/* A filter builder that takes its keys in batches while a table fills
+ * (SSTableWriter::Add -> FilterBlockWriter::Update, src/sstable.cpp:28,
+ * src/filter_block.cpp:72-75) and builds at the end (FilterBlockWriter::Final,
+ * src/filter_block.cpp:104-109, src/sstable.cpp:58).  Every appended key is
+ * hashed on arrival; the object keeps the two murmur hashes of each key, 8
+ * bytes, in one device array in key order, and the filter bounds on the host.
+ * A finish builds every filter from those pairs: it uploads and hashes
+ * nothing.  The bitmaps are those adl_bloom_build_segmented_device_ex gives
+ * for the same keys and bounds, bit for bit.
+ *
+ * Not thread-safe: one thread at a time per object; different objects may be
+ * used from different threads concurrently.  Buffers an object has outgrown
+ * are released by a reset once its appends and finishes have completed, and
+ * otherwise when it is destroyed. */
+typedef struct adl_bloom_stream adl_bloom_stream;
+
+/* Keys per workgroup of the append kernel for keys that are not aligned
+ * 16-byte keys (tests place batch sizes around it). */
+#define ADL_BLOOM_STREAM_RUN_KEYS 512
+
+/* reserve_keys: pairs the first allocation has room for (a hint; the store
+ * grows geometrically, the copy ordered on the growing append's stream).
+ * Nothing is allocated before the first append. */
+int adl_bloom_stream_create(uint64_t reserve_keys, adl_bloom_stream **stream_out);
+/* Waits for the object's appends and finishes in flight. */
+int adl_bloom_stream_destroy(adl_bloom_stream *s);
+/* Empties the object (no keys, no filters) and keeps its capacity. */
+int adl_bloom_stream_reset(adl_bloom_stream *s);
+
+/* Append n HOST keys, (keys, offsets | stride) as in adl_bloom_build, to the
+ * open filter.  The batch is copied into the calling thread's pinned staging;
+ * its upload and hashing are enqueued on `stream` and the call returns without
+ * waiting for the device (it waits only when the thread's staging slots are all
+ * in flight).  h_keys / h_offsets may be reused on return.  n == 0: no-op.
+ * Offsets that decrease: ADL_ERR_INVALID_ARG.  stream == NULL: the calling
+ * thread's own non-blocking stream, as for the other host-pointer calls. */
+int adl_bloom_stream_append(adl_bloom_stream *s, const uint8_t *h_keys, const uint64_t *h_offsets, uint64_t n,
+                            uint32_t key_stride, void *stream);
+
+/* The same for a DEVICE-resident batch, under the build's read contract: a
+ * 16-byte-aligned d_keys may be read up to 15 bytes past the batch's last key;
+ * of any other d_keys no byte outside the batch's keys is read.  The batch
+ * must stay untouched until the stream's work is done. */
+int adl_bloom_stream_append_device(adl_bloom_stream *s, const uint8_t *d_keys, const uint64_t *d_offsets,
+                                   uint64_t n, uint32_t key_stride, void *stream);
+
+/* Close the open filter, as FilterBlockWriter::Keys2Block() does.  Cuts with
+ * no key between them make empty filters. */
+int adl_bloom_stream_cut(adl_bloom_stream *s);
+
+/* The filters so far: *num_filters, and (key_begin != NULL) their bounds,
+ * num_filters + 1 entries (capacity smaller: ADL_ERR_INVALID_ARG, with
+ * *num_filters set).  Keys after the last cut count as a last filter, as
+ * Final's implicit Keys2Block does. */
+int adl_bloom_stream_counts(const adl_bloom_stream *s, uint32_t *num_filters, uint64_t *key_begin,
+                            uint32_t capacity);
+
+/* adl_bloom_build_workspace_bytes of the object's filters as they stand. */
+uint64_t adl_bloom_stream_finish_workspace_bytes(const adl_bloom_stream *s, int32_t bits_per_key);
+
+/* Build every filter of the object from its pairs: filter f's bitmap goes to
+ * d_bitmaps + bitmap_off[f] (HOST array, one entry per filter of
+ * adl_bloom_stream_counts).  Bitmaps, workspace, flags
+ * (ADL_BLOOM_SKIP_ADJACENT_DUPLICATES: a key whose pair equals its
+ * predecessor's is skipped, the same bitmap), launch-group split and statuses
+ * are those of adl_bloom_build_segmented_device_ex; an object without a filter
+ * is ADL_ERR_INVALID_ARG, a short workspace ADL_ERR_WORKSPACE with nothing
+ * enqueued.  Enqueued on `stream` behind every earlier append of the object,
+ * whatever stream that ran on.  The object is not consumed: it may be
+ * appended to and finished again, also with another bits_per_key. */
+int adl_bloom_stream_finish_device(adl_bloom_stream *s, int32_t bits_per_key, uint32_t flags, uint8_t *d_bitmaps,
+                                   const uint64_t *bitmap_off, void *d_workspace, uint64_t workspace_bytes,
+                                   void *stream);
+
+/* The same into HOST memory: filter f's bitmap, exactly
+ * adl_bloom_bitmap_bytes(n_f, bpk) bytes, at h_bitmaps + h_bitmap_off[f] (any
+ * alignment), as adl_bloom_build_segmented_ex writes them.  Synchronous
+ * (stream == NULL: the calling thread's own stream). */
+int adl_bloom_stream_finish(adl_bloom_stream *s, int32_t bits_per_key, uint32_t flags, uint8_t *h_bitmaps,
+                            const uint64_t *h_bitmap_off, void *stream);
+
 /* ------------------------------------------------- filter block on the device */
 
 /* Size of the filter block FilterBlockWriter::Final (src/filter_block.cpp:77-102)
@@ -760,6 +843,20 @@ int adl_bloom_filter_cache_build_device(adl_bloom_filter_cache *cache, const uin
                                         uint32_t flags, void *d_workspace, uint64_t workspace_bytes,
                                         uint8_t *h_block, uint64_t block_bytes, adl_bloom_cache_ticket **ticket,
                                         void *stream);
+
+/* adl_bloom_filter_cache_build with a stream (adl_bloom_stream, above) as its
+ * key source: the filters of adl_bloom_stream_counts are built from the
+ * stream's hash pairs straight into the reserved range -- nothing is uploaded
+ * or hashed -- and the block, the bytes adl_bloom_filter_cache_build writes
+ * for the same keys and bounds, goes to h_block.  *block_bytes receives its
+ * length (block_capacity smaller: ADL_ERR_INVALID_ARG, with *block_bytes
+ * set).  Flags, statuses and the ticket's publish / abandon life cycle are
+ * adl_bloom_filter_cache_build's; ADL_BLOOM_CACHE_VERIFY probes every pair
+ * again.  Runs behind every earlier append of the stream; the stream is not
+ * consumed.  Synchronous (stream == NULL: the calling thread's own stream). */
+int adl_bloom_filter_cache_build_stream(adl_bloom_filter_cache *cache, adl_bloom_stream *s, int32_t bits_per_key,
+                                        uint32_t flags, uint8_t *h_block, uint64_t block_capacity,
+                                        uint64_t *block_bytes, adl_bloom_cache_ticket **ticket, void *stream);
 
 /* Make the built block the most recently used block of table `oid`,
  * replacing one cached under that oid; max_tables is enforced as in put.
