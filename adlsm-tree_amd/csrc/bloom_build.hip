@@ -259,6 +259,18 @@ __device__ uint64_t g_stamps[3][2048][8];  // pass A, pass B, hashing pass
     if (threadIdx.x == 0 && blockIdx.x < 2048)                                    \
       for (int i_ = 0; i_ < 8; ++i_) g_stamps[pass][blockIdx.x][i_] = st_acc_[i_]; \
   } while (0)
+// Pass A's rounds (tools/pass_a_rounds.py): wave 0 of the first 256
+// workgroups stores s_memrealtime (100 MHz: time, where s_memtime counts the
+// XCD's own clock) at kernel entry [0], at the top of chunk step r [1 + r],
+// at the end of the loop and after the last chunk's store (the two entries
+// after the last step's); adl_bloom_debug_rounds() copies them.
+constexpr int kRoundStamps = 256;
+__device__ uint64_t g_rounds[256][kRoundStamps];
+#define ROUND_STAMP(i)                                                                 \
+  do {                                                                                 \
+    if (threadIdx.x == 0 && blockIdx.x < 256 && (uint32_t)(i) < (uint32_t)kRoundStamps) \
+      g_rounds[blockIdx.x][i] = __builtin_amdgcn_s_memrealtime();                      \
+  } while (0)
 // hash_run's hook: STAMP(i) after phase i; exp & 16: no hashing (wrong pairs)
 struct StampHook {
   uint64_t *acc, *t;
@@ -275,6 +287,7 @@ struct StampHook {
 #define STAMP_DECL
 #define STAMP(i) do { } while (0)
 #define STAMP_FLUSH(pass) do { } while (0)
+#define ROUND_STAMP(i) do { } while (0)
 #define STAMP_HOOK(a) RunNoHook{}
 #endif
 
@@ -723,10 +736,16 @@ __global__ __launch_bounds__(BLOCK) kPassARegs void bloom_bin16_kernel(BuildArgs
   constexpr int TPT = (int)((kHistMax + BLOCK - 1) / BLOCK);  // table entries per thread, at most
 
   using Raw = typename Src::Raw;
+  // A chunk index past the end (the last two steps of a workgroup prefetch
+  // nothing that is used) loads the launch's last chunk; every lane then loads
+  // that chunk's key 0, one 16-byte request per wave instead of a chunk's
+  // worth of keys that nobody hashes.
   auto fetch = [&](uint32_t chunk, Raw (&raw)[KPT]) {
+    const bool past = chunk >= total_chunks;
+    chunk = min(chunk, total_chunks - 1);
     const auto &d = FT::at(a, ft, FT::of_chunk(a, ft, chunk));
     const uint32_t first = (chunk - d.chunk_base) * C;
-    const uint32_t last = min(C, d.n - first) - 1u;
+    const uint32_t last = past ? 0u : min(C, d.n - first) - 1u;
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
       const uint32_t idx = min((uint32_t)(tid + i * BLOCK), last);
@@ -758,10 +777,9 @@ __global__ __launch_bounds__(BLOCK) kPassARegs void bloom_bin16_kernel(BuildArgs
     __syncthreads();  // read before qa is written again
   }
   if (wg0 >= total_chunks) return;
+  ROUND_STAMP(0);
   fetch(wg0, raw);
-#pragma unroll
-  for (int i = 0; i < KPT; ++i) Src::hash(raw[i], h1[i], h2[i]);
-  fetch(min(n1, total_chunks - 1), raw);
+  // (the LDS is set up while chunk 0's keys are on their way)
   for (uint32_t i = tid; i < a.hist_words; i += BLOCK) hist[i] = 0;
   if constexpr (CL)
     for (uint32_t i = tid; i < a.hist_words + 4; i += BLOCK) hist2[i] = 0;  // and the flags
@@ -780,11 +798,15 @@ __global__ __launch_bounds__(BLOCK) kPassARegs void bloom_bin16_kernel(BuildArgs
   uint32_t *dtab32 = after;
   if (dd)
     for (uint32_t i = tid; i < (2u << dd); i += BLOCK) dtab32[i] = ~0u;
+#pragma unroll
+  for (int i = 0; i < KPT; ++i) Src::hash(raw[i], h1[i], h2[i]);
+  fetch(n1, raw);
 
   uint4 *pdst = dummy4;  // deferred store of the previous chunk
   uint32_t ptotal = 0;
   uint32_t par = 0;  // CL: counter array / overflow flag of this chunk
   uint32_t qpar = 0;  // DYN: qa slot of this step
+  [[maybe_unused]] uint32_t rnd = 0;  // diagnostics build: this workgroup's step
   STAMP_DECL
   for (uint32_t wg = wg0; wg < total_chunks;) {
     [[maybe_unused]] uint32_t n3 = 0;
@@ -799,6 +821,7 @@ __global__ __launch_bounds__(BLOCK) kPassARegs void bloom_bin16_kernel(BuildArgs
     if (CL && par) hcur = hist2, hoth = hist;
     const uint32_t tcap = CL ? (a.cap / T) & ~3u : 0u;  // slots per tile (the plan keeps it >= 4)
     __syncthreads();  // hist cleared; the previous scatter is complete in lpos
+    ROUND_STAMP(1 + rnd);
     STAMP(0);
 
     // count(c) + store(c-1)
@@ -908,7 +931,7 @@ __global__ __launch_bounds__(BLOCK) kPassARegs void bloom_bin16_kernel(BuildArgs
 #endif
         Src::hash(raw[i], h1[i], h2[i]);
     }
-    fetch(min(n2, total_chunks - 1), raw);
+    fetch(n2, raw);
     // the repeated-hash table holds one filter's keys (positions depend on m)
     const bool last_of_filter = n1 >= total_chunks || FT::of_chunk(a, ft, n1) != fcur;
     if (CL && ovf) oflag[par] = 1u;
@@ -996,12 +1019,18 @@ __global__ __launch_bounds__(BLOCK) kPassARegs void bloom_bin16_kernel(BuildArgs
     } else {
       n2 += G;
     }
+    ++rnd;
   }
+  ROUND_STAMP(1 + rnd);
   // epilogue: the last chunk's store
   const uint32_t pvec = ptotal >> 2;
   for (uint32_t v = tid; v < pvec; v += BLOCK) pdst[v] = src4[v];
   if ((uint32_t)tid < (ptotal & 3u))
     reinterpret_cast<uint32_t *>(pdst)[pvec * 4 + tid] = lpos[pvec * 4 + tid];
+#ifdef ADL_BLOOM_STAMPS
+  __builtin_amdgcn_s_waitcnt(0);  // diagnostics: the last stores have left the wave's counters
+#endif
+  ROUND_STAMP(2 + rnd);
   STAMP(5);
   STAMP_FLUSH(0);
 }
@@ -1609,8 +1638,9 @@ int launch_binned_dt(const Plan &p, Keys keys, uint8_t *d_bitmaps, void *ws, hip
   BuildArgs ab = aa;
   ab.claim = claim_used;
   if (kn.debug)
-    fprintf(stderr, "adl_bloom launch: pass A %s (%s, %s), pass B %s (%u per CU, %s)\n", a_queued ? "queued" : "static",
-            a_kernel, DT ? "DT" : "kernarg", dyn_b ? "queued" : "static", p.occ_b, DT ? "DT" : "kernarg");
+    fprintf(stderr, "adl_bloom launch: pass A %s (%s, %s), pass B %s (%u per CU, %s); grids %u, %u\n",
+            a_queued ? "queued" : "static", a_kernel, DT ? "DT" : "kernarg", dyn_b ? "queued" : "static", p.occ_b,
+            DT ? "DT" : "kernarg", p.grid_a, p.grid_b);
   auto go_b = [&](auto lim, auto kern) -> int {
     if (int rc = lim()) return rc;
     hipExtLaunchKernelGGL(kern, dim3(p.grid_b), dim3(kBlockB), p.lds_b, st, ev ? ev[2] : nullptr,
@@ -1761,6 +1791,13 @@ int adl_bloom_debug_stamps(uint64_t *out, uint64_t n) {
   const uint64_t bytes = std::min<uint64_t>(n, kOwn) * 8;
   ADL_HIP_TRY(hipDeviceSynchronize());
   ADL_HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), bytes, 0, hipMemcpyDeviceToHost));
+  return ADL_OK;
+}
+// ... and g_rounds ([workgroup][stamp], the last launch of bloom_bin16_kernel).
+int adl_bloom_debug_rounds(uint64_t *out, uint64_t n) {
+  const uint64_t bytes = std::min<uint64_t>(n, 256ull * kRoundStamps) * 8;
+  ADL_HIP_TRY(hipDeviceSynchronize());
+  ADL_HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rounds), bytes, 0, hipMemcpyDeviceToHost));
   return ADL_OK;
 }
 #endif
