@@ -602,6 +602,13 @@ __attribute__((visibility("hidden"))) int adl_build_pairs_device(
     const uint64_t *bitmap_off, uint32_t flags, bool hash_dedup, void *d_workspace, uint64_t workspace_bytes,
     hipStream_t st);
 
+// Library-internal (hash_pairs.hip): both hashes of n keys of any shape, pair i
+// (a uint2) at out[i].  whole: d_keys is 16-byte aligned and may be read in
+// whole 16-byte blocks; otherwise no byte outside the n keys is read.
+__attribute__((visibility("hidden"))) int hash_pairs_device(const uint8_t *d_keys, const uint64_t *d_offsets,
+                                                            uint32_t key_stride, uint64_t n, bool whole, uint2 *out,
+                                                            hipStream_t st);
+
 // Library-internal (filter_block_device.hip): adl_filter_block_build_into over
 // a streamed build's pairs instead of keys.
 __attribute__((visibility("hidden"))) int adl_filter_block_build_into_pairs(

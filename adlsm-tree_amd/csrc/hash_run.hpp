@@ -1,8 +1,8 @@
 // adlsm-tree_amd/csrc/hash_run.hpp -- both murmur hashes of a run of keys that
 // are not aligned 16-byte keys, hashed from LDS in length order.  The one run
-// hasher of the build (hash_var_kernel, bloom_build.hip), of the binned probe
-// (pb_hash_kernel, probe_binned.hip) and of a streamed build's appends
-// (stream_hash_run_kernel, stream_build.hip).
+// hasher: hash_var_kernel (bloom_build.hip) writes at the sorted slot in pass
+// A's chunk grid, hash_run_pairs_kernel (hash_pairs.hip) at the key's index for
+// a streamed build's appends and the binned probe's queries.
 //
 // A wave hashes 64 keys in lockstep, so it costs as much as its longest key;
 // keys sorted by exact length within a run of S keys give waves of nearly
@@ -80,9 +80,8 @@ struct RunNoHook {
   __device__ __forceinline__ static constexpr bool no_hash() { return false; }
 };
 
-// Output at the key's own index in the run: out[ix] = (h1, h2).  The binned
-// probe's query pairs (pb_hash_kernel) and a streamed build's pair store
-// (stream_hash_run_kernel, stream_build.hip) are both in key order.
+// Output at the key's own index in the run: out[ix] = (h1, h2), pairs in key
+// order (hash_run_pairs_kernel, hash_pairs.hip).
 struct PairsByIndex {
   uint2 *out;
   static constexpr bool kByIndex = true;

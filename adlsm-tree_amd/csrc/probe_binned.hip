@@ -51,7 +51,6 @@
 #include <algorithm>
 
 #include "bloom_common.hpp"
-#include "hash_run.hpp"
 
 using namespace adl_dev;
 
@@ -93,7 +92,7 @@ struct Plan {
   // workspace byte offsets
   uint32_t ng = 0;  // groups of kScanGroup blocks (K2)
   uint64_t o_desc, o_scal, o_cnt, o_start, o_gsum, o_cf, o_dest, o_hs, o_ent, o_tab, o_split, o_res, total;
-  uint64_t o_qh = 0;  // the queries' hash pairs in query order (pb_hash_kernel); keys that are not 16-byte keys only
+  uint64_t o_qh = 0;  // the queries' hash pairs in query order (hash_pairs_device); keys that are not 16-byte keys only
 };
 
 constexpr uint32_t kScanGroup = 64;  // blocks per column-sum group (K2)
@@ -412,22 +411,12 @@ __device__ __forceinline__ void load_runs(const uint32_t *cnt, const uint32_t *s
 // qh[i] at the query's own index i; K3 then takes the pairs instead of keys.
 // One workgroup per run of S consecutive queries, hashed from LDS in length
 // order (hash_run.hpp); the grid is ceil(n / S).  No byte outside the batch's
-// keys is read (ReadExactBytes; include/adl_bloom.h).
-constexpr int kPhBlk = 256;
-constexpr uint32_t kPhRun = 512;  // queries per run (the build's measured shape)
-
-using PhOut = PairsByIndex;  // at the query's own index
-
-template <uint32_t S, class Keys>
-__global__ __launch_bounds__(kPhBlk) void pb_hash_kernel(Keys keys, uint64_t n, uint2 *__restrict__ qh) {
-  const uint64_t q0 = (uint64_t)blockIdx.x * S;
-  const uint32_t cnt = (uint32_t)min((uint64_t)S, n - q0);
-  hash_run<S, kPhBlk>(keys, q0, cnt, ReadExactBytes{n}, PhOut{qh + q0});
-}
+// keys is read (ReadExactBytes; include/adl_bloom.h).  The launch is
+// hash_pairs_device (hash_pairs.hip), shared with the builds.
 
 // ---------------------------------------------------------------- K3
 // What K3 takes per query: the 16-byte key itself (hashed here), or the
-// (h1, h2) pair pb_hash_kernel left at the query's index.
+// (h1, h2) pair hash_pairs_device left at the query's index.
 struct SrcKeys16 {
   const uint4 *keys;
   using Raw = uint4;
@@ -1051,7 +1040,7 @@ __global__ __launch_bounds__(kGatherBlk) void pb_gather_kernel(const uint16_t *_
 }
 
 // The key shape of a batch: aligned 16-byte keys are hashed inside K3; the
-// other two go through pb_hash_kernel first.
+// other two go through hash_pairs_device first.
 enum class Shape { kKeys16, kVar, kStride };
 
 bool filters_and_size_ok(uint64_t n, uint32_t F) { return n < 0x7fffffffull && F >= 1 && F <= kMaxBucketFilters; }
@@ -1228,16 +1217,7 @@ int run_binned(const Plan &p, Shape shape, const uint8_t *d_keys, const uint64_t
                          dest, hs, exp);
       ADL_HIP_TRY(hipGetLastError());
     } else {
-      const dim3 runs((uint32_t)((n + kPhRun - 1) / kPhRun));
-      constexpr size_t kLds = run_lds_bytes<kPhRun>(true);
-      static_assert(kLds == 30736, "the run's LDS at the measured shape, with the index array");
-      if (shape == Shape::kVar)
-        hipLaunchKernelGGL((pb_hash_kernel<kPhRun, KeysVar>), runs, dim3(kPhBlk), kLds, st,
-                           KeysVar{d_keys, d_offsets}, n, qh);
-      else
-        hipLaunchKernelGGL((pb_hash_kernel<kPhRun, KeysStride>), runs, dim3(kPhBlk), kLds, st,
-                           KeysStride{d_keys, key_stride}, n, qh);
-      ADL_HIP_TRY(hipGetLastError());
+      if (int rc = adl_host::hash_pairs_device(d_keys, d_offsets, key_stride, n, /*whole=*/false, qh, st)) return rc;
       if (int rc = adl_host::lds_limit<pb_scatter_kernel<SrcPairs>>()) return rc;
       hipLaunchKernelGGL(pb_scatter_kernel<SrcPairs>, dim3(p.nb), dim3(kBlk), lds_k3, st, SrcPairs{qh}, d_filter_id, n,
                          F, p.nb, desc, cnt, start, dest, hs, exp);

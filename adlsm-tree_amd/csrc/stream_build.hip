@@ -12,15 +12,10 @@
 // the segmented build's two passes over those pairs (bloom_build.hip:
 // SrcP / KeysPair).  A finish uploads and hashes nothing.
 //
-// Append kernels, pairs written at store + base + i in key order:
-//   stream_hash16_kernel    aligned 16-byte keys, a lane per key (hash16),
-//                           coalesced 8-byte stores;
-//   stream_hash_run_kernel  every other shape: one workgroup per run of
-//                           kRunKeys keys through hash_run (hash_run.hpp) with
-//                           the output at the key's index, as the binned
-//                           probe's pb_hash_kernel.
-// A 16-byte-aligned key buffer is read in whole blocks (up to 15 bytes past
-// the batch's last key), any other one byte-exactly (include/adl_bloom.h).
+// An append hashes its batch with hash_pairs_device (hash_pairs.hip), pairs
+// written at store + count + i in key order.  A 16-byte-aligned key buffer is
+// read in whole blocks (up to 15 bytes past the batch's last key), any other
+// one byte-exactly (include/adl_bloom.h).
 //
 // Ordering: every append records the object's append event on its stream and
 // waits for the previous one (the store's growth and the upload buffer are
@@ -43,34 +38,8 @@
 #include <vector>
 
 #include "bloom_common.hpp"
-#include "hash_run.hpp"
 
-using namespace adl_dev;
-
-namespace {
-
-constexpr int kRunBlk = 256;
-constexpr uint32_t kRunKeys = ADL_BLOOM_STREAM_RUN_KEYS;  // keys per run (the build's measured shape)
 constexpr uint64_t kMinStoreKeys = 4096;
-
-__global__ __launch_bounds__(256) void stream_hash16_kernel(const uint4 *__restrict__ keys, uint64_t n,
-                                                            uint2 *__restrict__ out) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  uint32_t h1, h2;
-  hash16(load_nt(keys + i), h1, h2);
-  out[i] = make_uint2(h1, h2);
-}
-
-template <uint32_t S, class Keys, bool EXACT>
-__global__ __launch_bounds__(kRunBlk) void stream_hash_run_kernel(Keys keys, uint64_t n, uint2 *__restrict__ out) {
-  const uint64_t q0 = (uint64_t)blockIdx.x * S;
-  const uint32_t cnt = (uint32_t)min((uint64_t)S, n - q0);
-  if constexpr (EXACT) hash_run<S, kRunBlk>(keys, q0, cnt, ReadExactBytes{n}, PairsByIndex{out + q0});
-  else hash_run<S, kRunBlk>(keys, q0, cnt, ReadWholeBlocks{}, PairsByIndex{out + q0});
-}
-
-}  // namespace
 
 struct adl_bloom_stream {
   uint2 *store = nullptr;
@@ -140,26 +109,11 @@ int grow_inbox(adl_bloom_stream *s, uint64_t bytes) {
   return ADL_OK;
 }
 
-// The append kernels over a device-resident batch; `whole`: the key buffer
-// may be read in whole aligned 16-byte blocks.
+// Hashes a device-resident batch into the store; `whole`: the key buffer may
+// be read in whole aligned 16-byte blocks.
 int launch_append(adl_bloom_stream *s, const uint8_t *d_keys, const uint64_t *d_offsets, uint64_t n,
                   uint32_t key_stride, bool whole, hipStream_t st) {
-  uint2 *out = s->store + s->count;
-  constexpr size_t kLds = run_lds_bytes<kRunKeys>(true);
-  const dim3 runs((uint32_t)((n + kRunKeys - 1) / kRunKeys));
-  if (d_offsets) {
-    const KeysVar k{d_keys, d_offsets};
-    if (whole) hipLaunchKernelGGL((stream_hash_run_kernel<kRunKeys, KeysVar, false>), runs, dim3(kRunBlk), kLds, st, k, n, out);
-    else hipLaunchKernelGGL((stream_hash_run_kernel<kRunKeys, KeysVar, true>), runs, dim3(kRunBlk), kLds, st, k, n, out);
-  } else if (key_stride == 16 && whole) {
-    hipLaunchKernelGGL(stream_hash16_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<const uint4 *>(d_keys), n, out);
-  } else {
-    const KeysStride k{d_keys, key_stride};
-    if (whole) hipLaunchKernelGGL((stream_hash_run_kernel<kRunKeys, KeysStride, false>), runs, dim3(kRunBlk), kLds, st, k, n, out);
-    else hipLaunchKernelGGL((stream_hash_run_kernel<kRunKeys, KeysStride, true>), runs, dim3(kRunBlk), kLds, st, k, n, out);
-  }
-  ADL_HIP_TRY(hipGetLastError());
+  if (int rc = adl_host::hash_pairs_device(d_keys, d_offsets, key_stride, n, whole, s->store + s->count, st)) return rc;
   ADL_HIP_TRY(hipEventRecord(s->ev_app, st));
   s->app_used = true;
   s->fin_wait = false;  // this append waited for the finishes; later ones are ordered behind it

@@ -6,7 +6,7 @@ GPU.
 """
 import numpy as np
 
-RUN = 512  # queries per run of pb_hash_kernel (csrc/probe_binned.hip)
+RUN = 512  # queries per run of hash_run_pairs_kernel (csrc/hash_pairs.hip)
 
 
 def ragged(starts, lens):
@@ -100,7 +100,7 @@ def queries(filters, n, lens, seed, fixed=None, member_share=0.5):
 
 def length_sort_changes_every_run(want, lens):
     """True iff moving every answer to its key's place in the run's stable
-    sort by min(length, 511) -- the order pb_hash_kernel hashes a run in --
+    sort by min(length, 511) -- the order hash_run_pairs_kernel hashes a run in --
     changes the answers of every run of RUN queries."""
     n = len(want)
     run = np.arange(n) // RUN

@@ -601,6 +601,9 @@ def test_build_launch_group_split(dev, ab, oracle, knobs, capfd):
     the first 71 filters alone (exactly at the limit) one line and the same
     bitmaps.  A workspace one byte short is ADL_ERR_WORKSPACE before anything
     is launched.  adl_bloom_build_positions reads the last group's tables.
+    The 74 filters are then built once more from the same keys one byte past
+    a 16-byte boundary (fixed-stride keys, hashed from memory key by key):
+    group 2 again starts at a non-zero key_begin.
 
     adl_bloom_filter_block_build_device and the cache builds cannot reach the
     split: a block is capped at 2^31 bytes, fewer keys than the group limit
@@ -666,6 +669,18 @@ def test_build_launch_group_split(dev, ab, oracle, knobs, capfd):
     _assert_launch(lines[0], GENERIC, True)
     check(71)
     assert bool((out[int(boff[71]):] == 0xAB).all())
+
+    # the same keys one byte past a 16-byte boundary: the fixed-stride view
+    shifted = dev.empty(keys.numel() + 16, dtype=dev.uint8, device="cuda")
+    shifted[1:1 + keys.numel()] = keys.view(-1)
+    del keys
+    out.fill_(0xAB)
+    assert _segmented(dev, ab, shifted[1:], 16, kb, bpk, out, boff, ws, wsb) == 0
+    lines = _launches(capfd)
+    assert len(lines) == 2, lines
+    _assert_launch(lines[0], GENERIC, True)
+    _assert_launch(lines[1], GENERIC, False)
+    check(74)
 
 
 # ================================================================ 7. a filter cache above 4 GiB

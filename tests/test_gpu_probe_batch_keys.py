@@ -3,7 +3,7 @@ not aligned 16-byte keys.
 
 Variable-length keys (d_offsets) and fixed strides other than 16 take the
 tile-binned pipeline from ADL_BLOOM_PROBE_BATCH_VAR_MIN queries on:
-pb_hash_kernel (csrc/probe_binned.hip) hashes runs of 512 queries from LDS,
+hash_run_pairs_kernel (csrc/hash_pairs.hip) hashes runs of 512 queries from LDS,
 sorted by length, and leaves each (h1, h2) at its query's index; the rest of
 the pipeline is the 16-byte one.  Every answer here equals
 BloomFilter::IsKeyExists (src/filter_block.cpp:49-62) per query --

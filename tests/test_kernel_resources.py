@@ -38,7 +38,7 @@ def res():
 
 
 def test_every_kernel_found(res):
-    for frag in ("bloom_bin16_kernel", "bloom_tile_kernel", "hash_var_kernel", "pb_hash_kernel", "pb_tile_kernel",
+    for frag in ("bloom_bin16_kernel", "bloom_tile_kernel", "hash_var_kernel", "hash_run_pairs_kernel", "pb_tile_kernel",
                  "pb_bin_kernel", "pb_scatter_kernel", "bloom_probe_multi_kernel", "probe_server_kernel", "filter_block_pack_kernel"):
         assert any(frag in k for k in res), frag
 

@@ -130,7 +130,7 @@ def test_append_kernels_in_the_code_object():
     import kernel_resources
 
     res = kernel_resources.kernel_resources(adlbloom.LIB_PATH)
-    for frag in ("stream_hash16_kernel", "stream_hash_run_kernel", "bloom_bin16_kernelILi1024ELi6ENS_4SrcP",
+    for frag in ("hash16_pairs_kernel", "hash_run_pairs_kernel", "bloom_bin16_kernelILi1024ELi6ENS_4SrcP",
                  "8KeysPair"):
         found = {k: r for k, r in res.items() if frag in k}
         assert found, frag
@@ -138,5 +138,5 @@ def test_append_kernels_in_the_code_object():
             assert r["scratch"] == 0, (k, r)
             if "bloom_bin" in k:
                 assert r["vgpr"] <= 120, (k, r)
-    runs = [k for k in res if "stream_hash_run_kernel" in k]
+    runs = [k for k in res if "hash_run_pairs_kernel" in k]
     assert len(runs) == 4  # var-len and fixed stride, whole-block and exact reads
